@@ -10,7 +10,10 @@ losses stay in their non-saturated regime), seeded orthogonal weights.
 N > 1: events shard data-parallel (one per rank and step), gradients are all-reduced over RCCL
 (``parallel.py``); value = events all ranks processed / max-over-ranks wall time ("weak" scaling).
 
-One JSON line on stdout (rank 0):
+A plain run sets up, warms up, times ``--steps`` steps of configs[1] and prints one JSON line (rank 0) with ``metric``, ``value``
+(events/s), ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` and the losses of the last timed step.  ``--dump-outputs DIR``
+also writes what that last step computed (the five losses; G / D / G_ema state after it, a fixed seeded sample) as DIR/<name>.npy.
+``--full`` adds everything else:
 * ``roofline``: the kernel family with the largest share of GPU time.  ``achieved`` = ALGORITHMIC bytes (or FLOPs) of its
   launches -- the layer-granular figures of SURVEY 8d, ``tools/arch_calc.py``: conv bytes = 2 N (Hs Ws Cin + H W Cout) --
   divided by their HIP-event time measured in this run on the launch stream; ``launcher_accounted`` repeats the fraction with
@@ -18,6 +21,7 @@ One JSON line on stdout (rank 0):
   the committed rocprofv3 PMC passes (NOT measured in this run: see ``traffic_source``).
 * ``families``: every family with its HBM and MFMA fractions.
 * ``cpu_baseline``: the CPU oracle (plain PyTorch restatement of the reference step, oracle/) timed on this host.
+* ``dp_exchange_slack_ms`` (data parallel): a few steps with HIP-event pairs around the gradient exchange.
 * ``configs3`` (N = 1, unless --no-configs3): the same measurement for BASELINE configs[3] -- 4 events per GPU and step with
   DiffAugment + CR_DiffAug consistency regularisation + uniformity loss; ``configs4``: configs[1] with the fp8 conv path.
 """
@@ -209,6 +213,29 @@ def roofline_of(r, total_ms, pmc, pmc_src):
     return out
 
 
+DUMP_STATE_SAMPLE = 4_000_000      # elements per network state kept by --dump-outputs (3 networks x 16 MB + the losses < 64 MB)
+DUMP_SEED = 20240917               # fixed: the same element positions are sampled in every run and every build
+
+
+def timed_outputs(losses, nets):
+    """The arrays a caller of the timed train step receives: the five losses it returns (float64) and the post-step state of
+    G, D and G_ema -- every floating-point state_dict entry (parameters, BatchNorm / spectral-norm buffers) flattened in
+    state_dict order to float32; above DUMP_STATE_SAMPLE elements a fixed seeded sample of positions (sorted) is kept."""
+    out = {f"loss_{k}": np.array([v], dtype=np.float64) for k, v in losses.items()}
+    for name, net in nets.items():
+        flat = torch.cat([t.detach().reshape(-1).float().cpu() for t in net.state_dict().values() if t.is_floating_point()]).numpy()
+        if flat.size > DUMP_STATE_SAMPLE:
+            flat = flat[np.sort(np.random.default_rng(DUMP_SEED).choice(flat.size, DUMP_STATE_SAMPLE, replace=False))]
+        out[f"{name}_state"] = flat.astype(np.float32)
+    return out
+
+
+def write_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def measure(cfg, args, rank, world, local, tag):
     """Build the networks for ``cfg``, warm up, time ``args.steps`` steps, optionally time every kernel family."""
     import _hip
@@ -220,11 +247,16 @@ def measure(cfg, args, rank, world, local, tag):
     E = int(cfg.get("events_per_step", 1))
     force_dp = bool(os.environ.get("IEAGAN_FORCE_DP")) and dist.is_initialized()     # 1-rank rehearsal of the DP path
     utils.seed_rng(cfg["seed"])
+    # the seeded initialisation runs on the host: on one intra-op thread, so that its roundings (orthogonal init's QR) and with them
+    # the weights every run starts from do not depend on the thread count of the machine
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
     with contextlib.redirect_stdout(io.StringIO()):
         G = model.Generator(**cfg).to(dev)
         D = model.Discriminator(**cfg).to(dev)
         G_ema = model.Generator(**dict(cfg, skip_init=True, no_optim=True)).to(dev)
         ema = utils.apply_ema(G, G_ema, cfg["ema_decay"], cfg["ema_start"])
+    torch.set_num_threads(threads)
     GD = model.G_D(G, D)
     h, w = cfg["resolution"], cfg["resolution"] * cfg["H_base"]
     n_rot = 4
@@ -265,7 +297,8 @@ def measure(cfg, args, rank, world, local, tag):
             dist.barrier()
             torch.cuda.synchronize()
 
-    timing = not args.no_kernel_timing
+    # per-kernel timing is part of the full record (or asked for by --shape-tags); a plain run times the steps alone
+    timing = not args.no_kernel_timing and (args.full or args.shape_tags)
     eager_timing = timing and not cfg["hip_graph"]
     if eager_timing:            # eager mode: HIP events bracket every launch inside the timed region itself
         _hip.call("ieagan_prof_reset")
@@ -279,6 +312,8 @@ def measure(cfg, args, rank, world, local, tag):
     dt = time.perf_counter() - t0
     if eager_timing:
         _hip.prof_enable(False)
+    # what the last timed step handed its caller: read before any later pass (kernel timing, DP slack) moves the weights on
+    dumped = timed_outputs(out, {"G": G, "D": D, "G_ema": G_ema}) if (args.dump_outputs and tag == "configs1" and rank == 0) else None
     prof_steps = steps
     recs = None
     if timing and cfg["hip_graph"]:
@@ -308,7 +343,7 @@ def measure(cfg, args, rank, world, local, tag):
         dt = float(t.item())
     dp_slack = None
     sync = parallel.get_context()
-    if sync is not None:
+    if sync is not None and args.full:
         # data parallel: does the side stream's work (all-reduce + ortho + Adam + EMA) finish before the main stream asks for it?
         # HIP-event pairs (side stream done, main stream arrives at its wait) over a few steps AFTER the timed region.
         sync.trace = True
@@ -322,7 +357,7 @@ def measure(cfg, args, rank, world, local, tag):
         for i, o in enumerate(trace):
             print(f"[{tag}] step {i}: " + "  ".join(f"{k} {v:.4f}" for k, v in o.items()), file=sys.stderr)
     return dict(dt=dt, steps=steps, out=out, recs=recs, prof_steps=prof_steps, eager_timing=eager_timing, h=h, w=w, E=E,
-                timed_losses=trace[-steps:], dp_slack=dp_slack)
+                timed_losses=trace[-steps:], dp_slack=dp_slack, dumped=dumped)
 
 
 def kernel_report(res, m, args):
@@ -387,6 +422,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="the full record: per-kernel timing / roofline, configs[3] and configs[4], the CPU baseline, data-parallel slack "
+                         "(a plain run times configs[1] alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (losses, sampled G / D / G_ema state) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", choices=("sub", "full"), default="sub",
                     help="sub: 8 of 40 sensors x5 (tens of seconds); full: 40 sensors, 1 warm-up + 1 timed step (minutes, ~30 GB)")
@@ -464,7 +505,9 @@ def main():
         if res.get("roofline") and res.get("roofline_conv_mfma"):
             res["roofline"]["conv_mfma_frac"] = res["roofline_conv_mfma"]["frac"]
             res["roofline"]["conv_mfma_kernel"] = res["roofline_conv_mfma"]["kernel"]
-    if world == 1 and not args.no_configs3 and not args.only_configs3:
+    if m["dumped"] is not None:
+        write_outputs(args.dump_outputs, m["dumped"])
+    if world == 1 and args.full and not args.no_configs3 and not args.only_configs3:
         m3 = measure(cfg_for(3), args, rank, world, local, "configs3")
         r3 = {"workload": desc3, "value": m3["E"] * m3["steps"] / m3["dt"], "unit": "events/s", "steps": m3["steps"],
               "ms_per_step": 1e3 * m3["dt"] / m3["steps"], "events_per_gpu_per_step": m3["E"], "losses_last_step": m3["out"]}
@@ -478,7 +521,7 @@ def main():
                                        "with >= 1000 tile-blocks; tensors in HBM stay bf16, wgrad bf16", "value": m4["E"] * m4["steps"] / m4["dt"], "unit": "events/s",
                            "steps": m4["steps"], "ms_per_step": 1e3 * m4["dt"] / m4["steps"], "dtype": "fp8 (e4m3) operands / bf16 tensors",
                            "losses_last_step": m4["out"], "tolerance": "tests/test_networks_gpu.py::test_fp8_conv_path_forward_and_step_tolerance"}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(cfg_for(1), args.cpu_baseline)
     print(json.dumps(res))
     sys.stdout.flush()

@@ -286,31 +286,59 @@ _STUBS = {"torchvision/__init__.py": "from . import transforms, datasets, utils\
           "seaborn.py": "", "boost_histogram.py": "", "cv2.py": ""}
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/train.py"), reason="needs the reference checkout (this container only)")
+# A stand-in for a reference checkout, written by the test itself: the import block of the reference's train.py (:12-19) and
+# its ``--outputroot`` argument, the host-side ``utils`` sub-modules that block imports, and same-named copies of the accelerated
+# modules that fail when imported -- so the test shows that the package wins for those and the checkout for the rest.
+_CHECKOUT = {
+    "train.py": "import argparse\n"
+                "import layers\nimport model\nimport train_fns\nimport utils\n"
+                "import utils.configuration as cf\n"
+                "from utils.logging import MetricsLogger, Logger\n"
+                "from utils.dataloader import load_dataset\n"
+                "from utils.plot import plot_sim_heatmap\n"
+                "if __name__ == '__main__':\n"
+                "    parser = argparse.ArgumentParser()\n"
+                "    parser.add_argument('--outputroot', required=True, help='path to output')\n"
+                "    parser.add_argument('--dataroot', required=True, help='path to dataset')\n"
+                "    parser.parse_args()\n",
+    "utils/__init__.py": "raise ImportError('the checkout utils/__init__.py must be shadowed by the package')\n",
+    "utils/configuration.py": "def initialize_directories(configuration):\n    pass\n",
+    "utils/logging.py": "class MetricsLogger:\n    pass\nclass Logger:\n    pass\n",
+    "utils/dataloader.py": "def load_dataset(*a, **k):\n    pass\n",
+    "utils/plot.py": "def plot_sim_heatmap(*a, **k):\n    pass\n",
+    **{f"{m}.py": f"raise ImportError('the checkout {m}.py must be shadowed by the package')\n" for m in ("layers", "model", "train_fns")},
+}
+
+
 def test_reference_train_script_imports_resolve_through_dropin(tmp_path):
     """``python iea-gan_amd/dropin.py <reference>/train.py ...``.  Every import statement of the
     reference's train.py (:12-19) resolves -- the accelerated modules to this package, the host-side bookkeeping
-    sub-modules to the checkout -- and the names train.py uses exist with compatible signatures.  torchvision / seaborn
-    are absent from this image and stubbed as EMPTY modules for the import (test infrastructure only)."""
+    sub-modules to the checkout -- and the names train.py uses exist with compatible signatures.  The checkout is the
+    stand-in above (_CHECKOUT); torchvision / seaborn are stubbed as EMPTY modules for the import (test infrastructure only)."""
     stubs = tmp_path / "stubs"
     for rel, body in _STUBS.items():
         f = stubs / rel
         f.parent.mkdir(parents=True, exist_ok=True)
         f.write_text(body)
+    checkout = tmp_path / "checkout"
+    for rel, body in _CHECKOUT.items():
+        f = checkout / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text(body)
     env = dict(os.environ, PYTHONPATH=str(stubs), PYTHONDONTWRITEBYTECODE="1")
     dropin = os.path.join(ROOT, "iea-gan_amd", "dropin.py")
-    r = subprocess.run([sys.executable, dropin, "/root/reference/train.py", "--help"], env=env, capture_output=True, text=True,
+    r = subprocess.run([sys.executable, dropin, str(checkout / "train.py"), "--help"], env=env, capture_output=True, text=True,
                        timeout=300, cwd=str(tmp_path))
     assert r.returncode == 0 and "--outputroot" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
     probe = tmp_path / "probe.py"
-    probe.write_text(_PROBE % {"pkg": os.path.join(ROOT, "iea-gan_amd")})
+    probe.write_text(_PROBE % {"pkg": os.path.join(ROOT, "iea-gan_amd"), "checkout": str(checkout)})
     r = subprocess.run([sys.executable, str(probe)], env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert r.returncode == 0 and "probe ok" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
 
 
 _PROBE = r"""
 import inspect, os, sys
-sys.path[:0] = [%(pkg)r, "/root/reference"]
+sys.path[:0] = [%(pkg)r, %(checkout)r]
 import layers, model, train_fns, utils                      # reference train.py:12-15
 import utils.configuration as cf                            # :16
 from utils.logging import MetricsLogger, Logger             # :17
@@ -320,7 +348,7 @@ pkg = %(pkg)r
 for m in (layers, model, train_fns, utils):
     assert os.path.dirname(os.path.abspath(m.__file__)).startswith(pkg), m.__file__
 for m in (cf, sys.modules["utils.logging"], sys.modules["utils.dataloader"], sys.modules["utils.plot"]):
-    assert m.__file__.startswith("/root/reference/utils/"), m.__file__
+    assert m.__file__.startswith(os.path.join(%(checkout)r, "utils") + os.sep), m.__file__
 b = lambda f, *a, **k: inspect.signature(f).bind(*a, **k)
 G = D = E = z = y = sd = cfg = log = object()
 b(utils.seed_rng, 1)                                                                          # train.py:38
