@@ -19,6 +19,7 @@ CONV_NO_LDS_WEIGHTS = 2  # ieagan_conv_desc.flags bit: C = 64 / 128 3x3 layers t
 CONV_FORCE_GATHER = 1   # ieagan_conv_desc.flags bit (tests): route a 3x3 layer through the gather kernel
 B1_OCC2, B1_OCC3, B1_TP32 = 1, 2, 4  # ieagan_conv1x1_bwd_desc.flags bits (benchmarks)
 BWD_NO_REDUCE = 16      # ieagan_conv1x1_bwd / ieagan_conv3x3_bwd: the caller folds the dW slabs (ieagan_wgrad_reduce)
+PXD_BINS = 251          # bins of the ADC spectrum of ieagan_pxd_stats (csrc/pxd_stats.hip)
 PROLOGUE_BWD_SLOTS = 64  # include/ieagan_hip.h: IEAGAN_PROLOGUE_BWD_SLOTS
 AUG_SLOTS = 128         # include/ieagan_hip.h: IEAGAN_AUG_SLOTS (per-image partial-sum slots of the DiffAugment entry points)
 BNB_REPL = 8            # replicas of the per-image accumulators of a BatchNorm-backward dgrad launch (common.h)
@@ -75,7 +76,7 @@ class ProfRec(C.Structure):
                 ("flops", C.c_double), ("bytes", C.c_double), ("bytes_min", C.c_double)]
 
 
-ABI_VERSION = 11           # include/ieagan_hip.h: IEAGAN_ABI_VERSION
+ABI_VERSION = 12           # include/ieagan_hip.h: IEAGAN_ABI_VERSION
 i, f, l = C.c_int, C.c_float, C.c_long
 _SIGS = {
     "ieagan_abi_version": [],
@@ -141,6 +142,8 @@ _SIGS = {
     "ieagan_maxpool2_bwd": [vp, vp, vp, i, i, i, i, vp],
     "ieagan_gamma_residual_fwd": [vp, vp, vp, vp, l, vp],
     "ieagan_gamma_residual_bwd": [vp, vp, vp, vp, vp, l, vp],
+    "ieagan_pxd_stats": [vp, i, i, i, i, i, f, vp, vp, vp, vp, vp],
+    "ieagan_pxd_stats_scratch": [i, i, i],
     "ieagan_ortho_ksplit": [],
     "ieagan_ortho_grad": [vp, vp, vp, vp, i, vp, i, vp, l, f, vp],
     "ieagan_selftest_tr_read": [vp, vp, vp],

@@ -54,4 +54,7 @@ def default_config() -> dict:
     # metadata with the rest of the configuration.
     c.update(dp_real_first=True)
     c.update(sn_prefetch=True)           # spectral-norm passes issued ahead of time on a side stream (single-GPU default step)
+    # detector-level validation on rank 0 (train_fns.validate): every val_every iterations (0 = off) generate val_events
+    # events and compare occupancy / hit charge / ADC spectrum, cut at val_threshold ADU, with as many real events
+    c.update(val_every=0, val_events=100, val_threshold=7.0)
     return c

@@ -10,7 +10,9 @@ metric / singular-value logging and periodic checkpoints in the reference's file
 Data: ``--dataroot DIR`` with one ``*.npy`` per event (uint8 ``[40, 250, 768]`` detector images, or float32
 already in [-1, 1]); the pad(3 rows) -> lognorm255 -> +4e-3 U dequantisation -> [-1, 1] chain of the
 reference's loader (utils/dataloader.py:59-76, utils/norm.py:8-19) runs on the GPU.  ``--synthetic N`` trains on
-N generated events (no files).  Any default of ``defaults.default_config()`` can be overridden as ``--key value``.
+N generated events (no files).  ``--val_every K`` (uint8 events) runs the detector-level validation of
+``train_fns.validate`` on rank 0 every K iterations (``logs/validation_rank0.jsonl``).  Any default of
+``defaults.default_config()`` can be overridden as ``--key value``.
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N train.py ...`` (events are sharded
 over the ranks -- every rank takes ``len(events) // N`` per epoch, so all ranks issue the same collectives --
 gradients all-reduced over RCCL).
@@ -147,6 +149,18 @@ def run(cfg):
     train = train_fns.GAN_training_function(G, D, GD, z_, y_, ema, state, cfg, dev)
     y = torch.arange(cfg["n_classes"], device=dev).repeat(E)
     log = open(os.path.join(lroot, f"metrics_rank{rank}.jsonl"), "a") if rank == 0 else None
+    real_stats = val_log = last_val = None
+    if cfg["val_every"] > 0 and rank == 0:
+        # the real side of the detector-level validation, once: the first min(val_events, len(events)) events of this rank
+        real_acc = utils.PXDStatistics(n_sensors=cfg["n_classes"], threshold=cfg["val_threshold"], device=dev)
+        for ev in mine[:min(cfg["val_events"], len(mine))]:
+            ev = ev if isinstance(ev, np.ndarray) else np.load(ev)
+            if ev.dtype != np.uint8:
+                raise SystemExit(f"val_every > 0 needs uint8 detector events (ADC counts); got {ev.dtype} events already in network "
+                                 "range -- run without validation or provide the uint8 files")
+            real_acc.update(torch.from_numpy(ev))
+        real_stats = real_acc.result()
+        val_log = open(os.path.join(lroot, "validation_rank0.jsonl"), "a")
     t0 = time.time()
 
     def checkpoint():
@@ -174,9 +188,15 @@ def run(cfg):
                     rec.update(utils.get_singular_values(D, "D"))
                 log.write(json.dumps(rec) + "\n")
                 log.flush()
+            if real_stats is not None and state["itr"] % cfg["val_every"] == 0:
+                if parallel.get_context() is not None:
+                    parallel.quiesce()  # G's side-stream update and the EMA behind it have landed before the copy is evaluated
+                last_val = train_fns.validate(G, G_ema, real_stats, state, cfg, val_log)
             if state["itr"] % cfg["log_interval"] == 0 and rank == 0:
                 print(f"itr {state['itr']}  {(time.time() - t0) / state['itr']:.3f} s/itr  " +
-                      "  ".join(f"{k} {v:.4f}" for k, v in metrics.items()))
+                      "  ".join(f"{k} {v:.4f}" for k, v in metrics.items()) +
+                      ("" if last_val is None else f"  val@{last_val['itr']} " + "  ".join(
+                          f"{k} {last_val[k]:.4f}" for k in ("occ_rel_err", "charge_rel_err", "spectrum_w1"))))
             if state["itr"] % cfg["save_every"] == 0:
                 checkpoint()
             if cfg["max_iters"] and state["itr"] >= cfg["max_iters"]:
@@ -189,6 +209,8 @@ def run(cfg):
             if net.lr_sched is not None:
                 net.lr_sched.step()
     checkpoint()
+    if val_log is not None:
+        val_log.close()
     if rank == 0:
         print(f"done: {state['itr']} iterations, weights under {os.path.join(run_dir, 'weights')}")
     train.close()                       # graphs / side streams released before the process group and the interpreter go away

@@ -100,6 +100,58 @@ def test(G, D, G_ema, state_dict, config, test_log):
     test_log.log(itr=int(state_dict["itr"]), FID=float(FID))
 
 
+def generated_statistics(net, config, n_events):
+    """``utils.PXDStatistics`` over ``n_events`` events generated by ``net`` (eval mode when ``G_eval_mode``, no_grad, export epilogue).
+    The latents and ``rdof`` come from a ``torch.Generator`` of its own seeded with ``config['seed']``: the global generators are not
+    touched; the ``.training`` flags are restored.  No host synchronisation."""
+    dev = next(net.parameters()).device
+    n = int(config["n_classes"])
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(config["seed"]))
+    stats = utils.PXDStatistics(n_sensors=n, threshold=float(config["val_threshold"]), device=dev)
+    y = torch.arange(n, dtype=torch.long, device=dev)
+    was_training = net.training
+    if config["G_eval_mode"]:
+        net.eval()
+    try:
+        with torch.no_grad():
+            for _ in range(n_events):
+                z = torch.randn(n, net.dim_z, generator=gen, device=dev)
+                rdof = torch.randn(n, net.rdof_dim, generator=gen, device=dev)
+                stats.update(net(z, y, rdof=rdof, export=True))
+    finally:
+        net.train(was_training)
+    return stats
+
+
+def validate(G, G_ema, real_stats, state_dict, config, log=None):
+    """Detector-level validation (reference Evaluation/eval_all.py:75-120, for the generator being trained): generate
+    ``config['val_events']`` events with ``G_ema`` (``ema and use_ema``) or ``G``, in eval mode when ``G_eval_mode``, through the export
+    epilogue, accumulate their occupancy / hit-charge / ADC-spectrum tables on the device (``utils.PXDStatistics``) and compare them with
+    ``real_stats`` (a ``PXDStatistics`` or its ``result()``): one line ``{itr, n_events, which, occ_rel_err, charge_rel_err, spectrum_w1}``
+    in ``logs/validation_rank0.jsonl`` (``log``: an open file to write it to instead), and the same dict returned.
+
+    It observes and nothing else: the latents and ``rdof`` come from a ``torch.Generator`` of its own seeded with ``config['seed']``
+    (the same events every call, so the curve over a run compares like with like), an eval-mode pass writes neither the spectral-norm
+    iterates nor the BatchNorm running statistics, and the ``.training`` flags are restored.  One host synchronisation, at the end."""
+    import json
+    import os
+    which, net = ("G_ema", G_ema) if (config["ema"] and config["use_ema"] and G_ema is not None) else ("G", G)
+    real = real_stats.result() if isinstance(real_stats, utils.PXDStatistics) else real_stats
+    fake = generated_statistics(net, config, int(config["val_events"]))
+    rec = dict(itr=int(state_dict["itr"]), n_events=int(config["val_events"]), which=which, **utils.pxd_distance(real, fake.result()))
+    line = json.dumps(rec) + "\n"
+    if log is not None:
+        log.write(line)
+        log.flush()
+    else:
+        ldir = os.path.join(config["outputroot"], config["run_name"], "logs")
+        os.makedirs(ldir, exist_ok=True)
+        with open(os.path.join(ldir, "validation_rank0.jsonl"), "a") as f:
+            f.write(line)
+    return rec
+
+
 def GAN_training_function(G, D, GD, z_, y_, ema, state_dict, config, device):
     if config["pos_collected_numerator"]:
         raise NotImplementedError("pos_collected_numerator=True is not part of the MI355X path (reference default: False)")

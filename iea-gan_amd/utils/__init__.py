@@ -259,6 +259,115 @@ def frechet_distance(mu1, sigma1, mu2, sigma2):
     return float(diff.dot(diff) + torch.trace(s1) + torch.trace(s2) - 2.0 * w.clamp_min(0).sqrt().sum())
 
 
+# ---------------------------------------------------------------------------------------------------------
+# detector-level validation (reference Evaluation/eval_all.py:75-120): per-sensor occupancy, mean hit charge, ADC spectrum
+# ---------------------------------------------------------------------------------------------------------
+PXD_OCC_BINS = 200          # eval_all.py:78: bh.axis.Regular(200, 0, 0.02) over the per-image occupancy
+
+
+def pxd_bin_edges():
+    """The 252 edges of the 251 ADC-spectrum bins (eval_all.py:77): [-1, 1, 7, 8, 9, ..., 256]."""
+    return np.concatenate([np.array([-1.0, 1.0, 7.0]), np.linspace(8, 256, 249)])
+
+
+def pxd_bin_index(v):
+    """The bin rule of ``ieagan_pxd_stats`` restated on the host: ``v < 1 -> 0; v < 7 -> 1; else 2 + min(floor(v) - 7, 248)``.
+    Equals ``np.histogram(v, pxd_bin_edges())`` for every v in [-1, 256]."""
+    v = np.asarray(v, dtype=np.float64)
+    return np.where(v < 1, 0, np.where(v < 7, 1, 2 + np.minimum(np.floor(np.minimum(v, 255.0)) - 7, 248))).astype(np.int64)
+
+
+class PXDStatistics:
+    """Accumulator of the reference's per-event detector statistics (eval_all.py:75-101 ``get_stats``) over batches of sensor images in
+    detector units, ``[N, H, W]`` fp32 (``Generator(..., export=True)``) or uint8 (event files); image ``n`` is sensor
+    ``n % n_sensors``.  ``update`` is one HIP launch pair (csrc/pxd_stats.hip) on the current stream: it neither synchronises nor
+    copies to the host; ``result()`` does the single read-back."""
+
+    def __init__(self, n_sensors=40, threshold=7.0, device=None):
+        self.n_sensors, self.threshold = int(n_sensors), float(threshold)
+        self.device = torch.device(device) if device is not None else None
+        self.reset()
+
+    def reset(self):
+        self.spectrum = None            # int64 [S, 251] on the device (the kernel's 64-bit unsigned counters)
+        self.hits, self.charge, self.shape = [], [], None
+
+    def update(self, images):
+        H.require_gpu()
+        if images.dim() == 4 and images.shape[1] == 1:
+            images = images[:, 0]
+        if images.dim() != 3 or images.dtype not in (torch.float32, torch.uint8):
+            raise TypeError("PXDStatistics.update expects fp32 or uint8 sensor images [N, H, W] in detector units")
+        if images.shape[0] == 0 or images.shape[0] % self.n_sensors:
+            raise ValueError(f"PXDStatistics.update: {images.shape[0]} images are not whole events of {self.n_sensors} sensors")
+        if self.device is None:
+            self.device = images.device if images.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        x = images.to(self.device, non_blocking=True).contiguous()
+        N, Hh, Ww = x.shape
+        if self.shape is None:
+            self.shape = (Hh, Ww)
+        elif self.shape != (Hh, Ww):
+            raise ValueError(f"PXDStatistics.update: image size {(Hh, Ww)} differs from the accumulated {self.shape}")
+        if self.spectrum is None:
+            self.spectrum = torch.zeros(self.n_sensors, H.PXD_BINS, dtype=torch.int64, device=self.device)
+        hits = torch.empty(N, dtype=torch.int32, device=self.device)
+        charge = torch.empty(N, dtype=torch.float32, device=self.device)
+        scratch = torch.empty(H.lib().ieagan_pxd_stats_scratch(N, Hh, Ww), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            H.call("ieagan_pxd_stats", x.data_ptr(), int(x.dtype == torch.uint8), N, Hh, Ww, self.n_sensors, self.threshold,
+                   self.spectrum.data_ptr(), hits.data_ptr(), charge.data_ptr(), scratch.data_ptr(), H.stream())
+        self.hits.append(hits)
+        self.charge.append(charge)
+        return hits, charge
+
+    def result(self):
+        """NumPy tables: ``spectrum [S, 251]``, ``occupancy [S]`` (mean over events of hits / (H*W)), ``mean_charge [S]`` (mean over
+        the events in which the sensor had a hit of charge / hits; NaN for a sensor that never had one), ``occ_hist [200]`` over
+        [0, 0.02) of every per-image occupancy plus ``occ_overflow``, ``n_events``; and the per-image ``hits`` / ``charge`` ``[E, S]``.
+        The occupancy bin is ``(hits * 10000) // (H*W)`` in integers: a bin edge of ``linspace(0, 0.02, 201)`` is then decided
+        exactly, not by float rounding."""
+        if not self.hits:
+            raise RuntimeError("PXDStatistics.result() before any update()")
+        S = self.n_sensors
+        px = self.shape[0] * self.shape[1]
+        packed = torch.cat([self.spectrum.reshape(-1), torch.cat(self.hits).to(torch.int64),
+                            torch.cat(self.charge).view(torch.int32).to(torch.int64)]).cpu().numpy()      # the one device-to-host copy
+        spectrum = packed[:S * H.PXD_BINS].reshape(S, H.PXD_BINS).copy()
+        n = (packed.size - S * H.PXD_BINS) // 2
+        hits = packed[S * H.PXD_BINS:S * H.PXD_BINS + n].reshape(-1, S)
+        charge = packed[S * H.PXD_BINS + n:].astype(np.int32).view(np.float32).reshape(-1, S)
+        occupancy = (hits.astype(np.float64) / px).mean(0)
+        has = hits > 0
+        per = np.where(has, charge.astype(np.float64) / np.maximum(hits, 1), 0.0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean_charge = per.sum(0) / has.sum(0)
+        b = (hits.reshape(-1) * 10000) // px
+        occ_hist = np.bincount(b[b < PXD_OCC_BINS], minlength=PXD_OCC_BINS).astype(np.int64)
+        return dict(spectrum=spectrum, occupancy=occupancy, mean_charge=mean_charge, occ_hist=occ_hist,
+                    occ_overflow=int((b >= PXD_OCC_BINS).sum()), n_events=int(hits.shape[0]), hits=hits.copy(), charge=charge.copy())
+
+
+def pxd_distance(real, fake):
+    """Three distances between two ``PXDStatistics.result()`` tables (float64, host): ``occ_rel_err`` / ``charge_rel_err`` = mean over
+    the sensors with real occupancy > 0 of |fake - real| / real (a fake sensor that never had a hit counts with mean charge 0, i.e.
+    a relative error of 1); ``spectrum_w1`` = the 1-D Wasserstein distance in ADU between the hit spectra (bins 2 .. 250, one ADU
+    wide, pooled over the sensors, each normalised to 1), NaN when one side has no hit at all."""
+    def rel(r, f, ok):
+        r, f = np.asarray(r, np.float64), np.nan_to_num(np.asarray(f, np.float64), nan=0.0)
+        return float(np.mean(np.abs(f[ok] - r[ok]) / r[ok])) if ok.any() else float("nan")
+
+    occ_r = np.asarray(real["occupancy"], np.float64)
+    out = dict(occ_rel_err=rel(occ_r, fake["occupancy"], occ_r > 0),
+               charge_rel_err=rel(real["mean_charge"], fake["mean_charge"], occ_r > 0))
+    hr = np.asarray(real["spectrum"], np.float64)[:, 2:].sum(0)
+    hf = np.asarray(fake["spectrum"], np.float64)[:, 2:].sum(0)
+    if hr.sum() > 0 and hf.sum() > 0:
+        out["spectrum_w1"] = float(np.abs(np.cumsum(hf / hf.sum()) - np.cumsum(hr / hr.sum())).sum())
+    else:
+        out["spectrum_w1"] = float("nan")
+    return out
+
+
 def count_parameters(module):
     print("Number of parameters: {}".format(sum(p.data.nelement() for p in module.parameters())))
 

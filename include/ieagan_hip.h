@@ -19,7 +19,7 @@ extern "C" {
 #endif
 
 const char* ieagan_last_error(void);
-#define IEAGAN_ABI_VERSION 11       /* bumped whenever a struct layout or a signature in this header changes */
+#define IEAGAN_ABI_VERSION 12       /* bumped whenever a struct layout or a signature in this header changes */
 int ieagan_abi_version(void);        /* == IEAGAN_ABI_VERSION of the header the library was built from */
 
 /* ---- profiling hooks (bench.py): per-kernel HIP-event timing on the launch stream ---- */
@@ -392,6 +392,21 @@ int ieagan_event_ingest(const void* ev_u8, const float* noise, float* out, int N
  * derives the bias corrections on the device, so a captured HIP graph of the step stays valid. */
 int ieagan_adam_step(float* p, const float* g, float* m, float* v, long n, float* hp, void* stream);
 int ieagan_ema_update(float* tgt, const float* src, long n, const float* decay_dev, void* stream);
+
+/* ---- detector-level validation statistics (pxd_stats.hip) -------------------------------------------
+ * The per-batch part of the reference's physical acceptance test (Evaluation/eval_all.py:75-101 get_stats, :115 the 7 ADU cut)
+ * on a batch of sensor images in detector units, [N, H, W] fp32 (is_u8 = 0: what ieagan_conv_Cto1 with tanh_out = 2 returns)
+ * or uint8 (is_u8 = 1: event files).  Image n belongs to sensor n % n_sensors (N a multiple of n_sensors).  Per pixel
+ *   v' = v < threshold ? 0 : v          (the cut; the export epilogue's own cut at 6.78 ADU is not relied on)
+ *   hit = v' > 0                         (eval_all.py:89)
+ *   bin = v' < 1 ? 0 : v' < 7 ? 1 : 2 + min(floor(v') - 7, 248)      (edges [-1, 1, 7, 8, ..., 256] of eval_all.py:77: 251 bins)
+ * spectrum [n_sensors][251] 64-bit unsigned counters, ACCUMULATED across calls (the caller zeroes them once); every pixel is counted,
+ * non-hits in bin 0.  hits [N] int32 and charge [N] fp32 (sum of the hit values of the image) are overwritten.  Counters are exact;
+ * the charge is summed in a fixed order through one single-writer slot per workgroup (no float atomics): bit-identical run to run.
+ * scratch: ieagan_pxd_stats_scratch(N, H, W) floats, need not be zeroed. */
+int ieagan_pxd_stats(const void* images, int is_u8, int N, int H, int W, int n_sensors, float threshold,
+                     unsigned long long* spectrum, int* hits, float* charge, float* scratch, void* stream);
+long ieagan_pxd_stats_scratch(int N, int H, int W);
 
 /* ---- orthogonal regularisation (ortho.hip) -------------------------------------------------------
  * Replaces utils.ortho (reference utils/__init__.py:843-859) for ALL weight matrices of a network in one call:
