@@ -144,6 +144,8 @@ _SIGS = {
     "ieagan_gamma_residual_bwd": [vp, vp, vp, vp, vp, l, vp],
     "ieagan_pxd_stats": [vp, i, i, i, i, i, f, vp, vp, vp, vp, vp],
     "ieagan_pxd_stats_scratch": [i, i, i],
+    "ieagan_pxd_digits": [vp, i, i, i, i, f, l, vp, vp, vp, vp, vp, vp],
+    "ieagan_pxd_digits_scratch": [i, i, i],
     "ieagan_ortho_ksplit": [],
     "ieagan_ortho_grad": [vp, vp, vp, vp, i, vp, i, vp, l, f, vp],
     "ieagan_selftest_tr_read": [vp, vp, vp],

@@ -11,19 +11,9 @@
 // slots of an image in slot order, so the reported charge is bit-reproducible run to run (no float atomics).
 #include "common.h"
 
-#define PXD_BINS 251
-#define PXD_THREADS 256
-#define PXD_CHUNK 4096          // pixels per block at the least: 4 float4 / 1 x 16 uint8 per thread
-#define PXD_MAX_BLOCKS 2048
-#define PXD_MAX_PARTS 64
+#include "pxd_common.h"
 
-static inline int pxd_parts(int N, long HW) {
-    long p = (HW + PXD_CHUNK - 1) / PXD_CHUNK;
-    const long cap = PXD_MAX_BLOCKS / N > 1 ? PXD_MAX_BLOCKS / N : 1;
-    if (p > cap) p = cap;
-    if (p > PXD_MAX_PARTS) p = PXD_MAX_PARTS;
-    return (int)(p < 1 ? 1 : p);
-}
+#define PXD_BINS 251
 
 struct PxdAcc {
     int hits;

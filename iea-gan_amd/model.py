@@ -552,14 +552,27 @@ class Model(Generator):
         super().__init__(**config)
 
 
-def generate(model):
+def generate(model, sparse=False):
     """One event of 40 sensor images in detector units: [40, 250, 768] (reference model.py:1130-1148).  With this
     package's Generator the threshold / 256^x / clamp / crop run inside the last conv kernel and only the finished
-    event crosses PCIe; any other callable takes the reference's host-side post-processing."""
+    event crosses PCIe; any other callable takes the reference's host-side post-processing.
+
+    ``sparse=True`` returns what the reference's production path returns (Physics_Analysis/create_g1.py:62-79):
+    ``((sensor, ucell, vcell) lists, charges list)`` of the nonzero uint8 pixels in ``nonzero()`` order.  The event is
+    compacted on the device (``utils.pxd_digits``, threshold 0) and only the digits cross PCIe."""
     device = next(model.parameters()).device
     with torch.no_grad():
         latents = torch.randn(40, 128, device=device)
         labels = torch.arange(40, dtype=torch.long, device=device)
+        if sparse:
+            import utils
+            if isinstance(model, Generator):
+                imgs = model(latents, labels, export=True)
+            else:
+                imgs = F.threshold(model(latents, labels).detach().float(), -0.26, -1).mul_(0.5).add_(0.5)
+                imgs = torch.pow(256, imgs).add_(-1).clamp_(0, 255)[:, 0, 3:-3, :]
+            _, sensor, ucell, vcell, charge = utils.pxd_digits(imgs, threshold=0.0).unpack()
+            return (sensor.tolist(), ucell.tolist(), vcell.tolist()), charge.tolist()
         if isinstance(model, Generator):
             return model(latents, labels, export=True).cpu()
         imgs = model(latents, labels).detach().cpu()

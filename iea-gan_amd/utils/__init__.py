@@ -368,6 +368,148 @@ def pxd_distance(real, fake):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------
+# event production (reference Physics_Analysis/create_g1.py:62-79): sparse digits (sensor, u cell, v cell, charge)
+# ---------------------------------------------------------------------------------------------------------
+PXD_DIGITS_FRACTION = 16    # default capacity of pxd_digits: one digit per 16 pixels (6.25 %; PXD background sits near 1 %)
+
+
+class PXDDigits:
+    """Device-side result of ``pxd_digits``: ``index`` int32 ``[capacity]`` (flat position ``n*H*W + r*W + c``, ascending), ``charge``
+    uint8 ``[capacity]``, ``counts`` int32 ``[N]``, ``total`` int32 ``[1]`` -- only the first ``min(total, capacity)`` digits are
+    written.  ``start_copy`` enqueues the device-to-host copies, ``cpu()`` / ``unpack()`` wait for them (one wait)."""
+
+    def __init__(self, images, threshold, capacity, n_sensors, header, index, charge):
+        self.images, self.threshold, self.capacity, self.n_sensors = images, threshold, capacity, n_sensors
+        self.shape = tuple(images.shape)
+        self.header, self.index, self.charge = header, index, charge
+        self.counts, self.total = header[:self.shape[0]], header[self.shape[0]:]
+        self._host = None
+
+    def start_copy(self, expect=None, buffers=None):
+        """Enqueue the copy of the header (``counts``, ``total``) and of the first ``expect`` digits (default: ``capacity``) into
+        pinned host memory on the current stream, and record an event; does not wait.  ``buffers``: pinned tensors
+        ``(header int32 [>= N+1], index int32, charge uint8)`` to reuse instead of allocating."""
+        m = self.capacity if expect is None else max(0, min(int(expect), self.capacity))
+        N = self.shape[0]
+        if buffers is None:
+            buffers = (torch.empty(N + 1, dtype=torch.int32, pin_memory=True), torch.empty(m, dtype=torch.int32, pin_memory=True),
+                       torch.empty(m, dtype=torch.uint8, pin_memory=True))
+        hdr, idx, chg = buffers
+        if hdr.numel() < N + 1 or idx.numel() < m or chg.numel() < m:
+            raise ValueError("PXDDigits.start_copy: a host buffer is too short")
+        with torch.cuda.device(self.header.device):
+            hdr[:N + 1].copy_(self.header, non_blocking=True)
+            idx[:m].copy_(self.index[:m], non_blocking=True)
+            chg[:m].copy_(self.charge[:m], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self._host = (hdr, idx, chg, m, ev)
+        return self
+
+    def cpu(self):
+        """NumPy ``(index [total], charge [total], counts [N])``: waits once for the copies of ``start_copy`` (started here when the
+        caller did not).  Never truncated: when ``total`` exceeds the capacity the kernel is run again with ``capacity = total``, and
+        when it exceeds what was copied the rest is copied -- a second wait, on those paths only."""
+        if self._host is None:
+            self.start_copy()
+        hdr, idx, chg, m, ev = self._host
+        ev.synchronize()
+        N = self.shape[0]
+        counts, total = hdr[:N].numpy().copy(), int(hdr[N])
+        if total > self.capacity:
+            full = pxd_digits(self.images, self.threshold, capacity=total, n_sensors=self.n_sensors)
+            self.capacity, self.header, self.index, self.charge = total, full.header, full.index, full.charge
+            self.counts, self.total = full.counts, full.total
+            return self.index.cpu().numpy(), self.charge.cpu().numpy(), counts
+        index, charge = idx[:min(m, total)].numpy().copy(), chg[:min(m, total)].numpy().copy()
+        if total > m:
+            index = np.concatenate([index, self.index[m:total].cpu().numpy()])
+            charge = np.concatenate([charge, self.charge[m:total].cpu().numpy()])
+        return index, charge, counts
+
+    def unpack(self):
+        """NumPy ``(event, sensor, ucell, vcell, charge)`` of every digit, in ascending flat index: image ``n`` is sensor
+        ``n % n_sensors`` of event ``n // n_sensors``, ``ucell`` the row and ``vcell`` the column (create_g1.py:77, :106)."""
+        index, charge, _ = self.cpu()
+        return unpack_digits(index, charge, self.shape, self.n_sensors)
+
+
+def unpack_digits(index, charge, shape, n_sensors=40):
+    """Flat digit positions of an ``[N, H, W]`` batch -> ``(event, sensor, ucell, vcell, charge)`` arrays."""
+    N, Hh, Ww = shape
+    index = np.asarray(index)
+    if index.dtype != np.int32:                 # the kernel's own int32 positions are split in int32 (N*H*W < 2^31)
+        index = index.astype(np.int64)
+    n, rest = np.divmod(index, index.dtype.type(Hh * Ww))
+    r, c = np.divmod(rest, index.dtype.type(Ww))
+    return ((n // n_sensors).astype(np.int32), (n % n_sensors).astype(np.uint8 if n_sensors <= 256 else np.int32),
+            r.astype(np.uint8 if Hh <= 256 else np.uint16), c.astype(np.uint16), np.asarray(charge, np.uint8))
+
+
+def pxd_digits(images, threshold=0.0, capacity=None, n_sensors=40):
+    """Sparse digits of a batch of sensor images in detector units, ``[N, H, W]`` fp32 (``Generator(..., export=True)``) or uint8 (event
+    files), compacted on the device (csrc/pxd_digits.hip): the reference's ``.to(uint8)`` / ``nonzero()`` / gather
+    (Physics_Analysis/create_g1.py:73-79) without the dense tensor crossing PCIe.  A pixel is a digit iff its truncated charge
+    ``q = uint8(min(max(v, 0), 255))`` is positive and ``v >= threshold`` (0: the reference's production behaviour, 7: the evaluation
+    cut); digits come in ascending flat index, the order of ``torch.nonzero``, bit-identical run to run.
+
+    Launches on the current stream, neither synchronises nor copies; with ``capacity`` given it can be captured into a HIP graph.
+    ``capacity`` (digits) defaults to one per 16 pixels (``N*H*W // 16``, at least 1024).  ``counts`` and ``total`` of the returned
+    ``PXDDigits`` always hold the true numbers; its ``cpu()`` / ``unpack()`` rerun with a larger capacity instead of truncating."""
+    H.require_gpu()
+    if images.dim() == 4 and images.shape[1] == 1:
+        images = images[:, 0]
+    if images.dim() != 3 or images.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("pxd_digits expects fp32 or uint8 sensor images [N, H, W] in detector units")
+    if images.shape[0] == 0 or images.shape[0] % n_sensors:
+        raise ValueError(f"pxd_digits: {images.shape[0]} images are not whole events of {n_sensors} sensors")
+    dev = images.device if images.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    x = images.to(dev, non_blocking=True).contiguous()
+    N, Hh, Ww = x.shape
+    if N * Hh * Ww >= 2 ** 31:
+        raise ValueError(f"pxd_digits: {N} x {Hh} x {Ww} pixels do not fit the int32 flat index; split the batch")
+    capacity = max(1024, N * Hh * Ww // PXD_DIGITS_FRACTION) if capacity is None else int(capacity)
+    if capacity < 0:
+        raise ValueError("pxd_digits: capacity is negative")
+    header = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    index = torch.empty(capacity, dtype=torch.int32, device=dev)
+    charge = torch.empty(capacity, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(H.lib().ieagan_pxd_digits_scratch(N, Hh, Ww), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        H.call("ieagan_pxd_digits", x.data_ptr(), int(x.dtype == torch.uint8), N, Hh, Ww, float(threshold), capacity,
+               index.data_ptr() if capacity else None, charge.data_ptr() if capacity else None, header.data_ptr(),
+               header.data_ptr() + 4 * N, scratch.data_ptr(), H.stream())
+    return PXDDigits(x, float(threshold), capacity, int(n_sensors), header, index, charge)
+
+
+def write_digits(path, event_offsets, sensor, ucell, vcell, charge):
+    """The event file of ``produce.py`` (``.npz``): ``event_offsets`` int64 ``[events + 1]`` (the digits of event ``e`` are
+    ``[event_offsets[e], event_offsets[e + 1])``), ``sensor`` uint8, ``ucell`` uint8, ``vcell`` uint16, ``charge`` uint8."""
+    event_offsets = np.asarray(event_offsets, np.int64)
+    cols = dict(sensor=np.asarray(sensor), ucell=np.asarray(ucell), vcell=np.asarray(vcell), charge=np.asarray(charge))
+    if event_offsets.ndim != 1 or event_offsets.size < 1 or event_offsets[0] != 0 or (np.diff(event_offsets) < 0).any():
+        raise ValueError("write_digits: event_offsets must start at 0 and not decrease")
+    for k, v in cols.items():
+        if v.ndim != 1 or v.size != event_offsets[-1]:
+            raise ValueError(f"write_digits: {k} has {v.size} entries, event_offsets ends at {event_offsets[-1]}")
+    if cols["sensor"].size and (cols["sensor"].max() > 255 or cols["ucell"].max() > 255 or cols["vcell"].max() > 65535):
+        raise ValueError("write_digits: a sensor / ucell / vcell value does not fit the file's uint8 / uint8 / uint16 columns")
+    with open(path, "wb") as fh:
+        np.savez(fh, event_offsets=event_offsets, sensor=cols["sensor"].astype(np.uint8), ucell=cols["ucell"].astype(np.uint8),
+                 vcell=cols["vcell"].astype(np.uint16), charge=cols["charge"].astype(np.uint8))
+
+
+def read_digits(path):
+    """Yields the events of a ``produce.py`` file in the format ``create_g1.generate`` puts on its queue (create_g1.py:79, read by
+    ``DigitCreator.event`` :105-106): ``((sensor, ucell, vcell) lists, charges list)``."""
+    with np.load(path) as t:
+        off, sensor, ucell, vcell, charge = (t[k] for k in ("event_offsets", "sensor", "ucell", "vcell", "charge"))
+    for e in range(off.size - 1):
+        s = slice(int(off[e]), int(off[e + 1]))
+        yield (sensor[s].tolist(), ucell[s].tolist(), vcell[s].tolist()), charge[s].tolist()
+
+
 def count_parameters(module):
     print("Number of parameters: {}".format(sum(p.data.nelement() for p in module.parameters())))
 

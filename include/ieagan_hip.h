@@ -408,6 +408,20 @@ int ieagan_pxd_stats(const void* images, int is_u8, int N, int H, int W, int n_s
                      unsigned long long* spectrum, int* hits, float* charge, float* scratch, void* stream);
 long ieagan_pxd_stats_scratch(int N, int H, int W);
 
+/* ---- event production: sparse digits (pxd_digits.hip) -----------------------------------------------
+ * The tail of the reference's production path (Physics_Analysis/create_g1.py:73-79: clamp, .to(uint8), nonzero(), gather) on a batch
+ * of sensor images in detector units, [N, H, W] fp32 (is_u8 = 0) or uint8 (is_u8 = 1), N * H * W < 2^31.  Per pixel
+ *   q = (uint8) trunc(min(max(v, 0), 255))   (NaN -> 0; uint8 input: q = v);      digit iff q > 0 && v >= threshold
+ * (threshold 0: the reference's production behaviour; 7: the evaluation cut).  Digit k, in ASCENDING flat index (the order of
+ * torch.nonzero on the uint8 tensor): index[k] = n*H*W + r*W + c (int32), charge[k] = q.  counts [N] int32 digits per image and
+ * total [1] int32 always hold the true numbers; digits with k >= capacity are dropped and nothing is written outside
+ * index[0:capacity] / charge[0:capacity] (capacity 0: counting only, index / charge may be NULL).  No atomic decides a position:
+ * two calls on the same input write the same bytes.
+ * scratch: ieagan_pxd_digits_scratch(N, H, W) int32 words, need not be zeroed. */
+long ieagan_pxd_digits_scratch(int N, int H, int W);
+int ieagan_pxd_digits(const void* images, int is_u8, int N, int H, int W, float threshold, long capacity,
+                      int* index, unsigned char* charge, int* counts, int* total, int* scratch, void* stream);
+
 /* ---- orthogonal regularisation (ortho.hip) -------------------------------------------------------
  * Replaces utils.ortho (reference utils/__init__.py:843-859) for ALL weight matrices of a network in one call:
  * grad[l] += 2*strength * ((W_l W_l^T) (.) (1 - I)) W_l, fp32, on the flat parameter / gradient arenas.
