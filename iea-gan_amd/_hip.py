@@ -20,6 +20,10 @@ CONV_FORCE_GATHER = 1   # ieagan_conv_desc.flags bit (tests): route a 3x3 layer 
 B1_OCC2, B1_OCC3, B1_TP32 = 1, 2, 4  # ieagan_conv1x1_bwd_desc.flags bits (benchmarks)
 BWD_NO_REDUCE = 16      # ieagan_conv1x1_bwd / ieagan_conv3x3_bwd: the caller folds the dW slabs (ieagan_wgrad_reduce)
 PXD_BINS = 251          # bins of the ADC spectrum of ieagan_pxd_stats (csrc/pxd_stats.hip)
+# columns of one sensor's row of the ieagan_pxd_cluster_stats tables (csrc/pxd_clusters.hip): name -> (first column, bins)
+PXD_CLUSTER_COLUMNS = {"size_spectrum": (0, 64), "charge_spectrum": (64, 256), "seed_spectrum": (320, 256), "size_u_spectrum": (576, 32),
+                       "size_v_spectrum": (608, 32)}
+PXD_CLUSTER_BINS = 640
 PROLOGUE_BWD_SLOTS = 64  # include/ieagan_hip.h: IEAGAN_PROLOGUE_BWD_SLOTS
 AUG_SLOTS = 128         # include/ieagan_hip.h: IEAGAN_AUG_SLOTS (per-image partial-sum slots of the DiffAugment entry points)
 BNB_REPL = 8            # replicas of the per-image accumulators of a BatchNorm-backward dgrad launch (common.h)
@@ -146,6 +150,9 @@ _SIGS = {
     "ieagan_pxd_stats_scratch": [i, i, i],
     "ieagan_pxd_digits": [vp, i, i, i, i, f, l, vp, vp, vp, vp, vp, vp],
     "ieagan_pxd_digits_scratch": [i, i, i],
+    "ieagan_pxd_clusters": [vp, vp, vp, i, i, i, l, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "ieagan_pxd_clusters_scratch": [i, i, i, l],
+    "ieagan_pxd_cluster_stats": [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, l, vp, vp, vp],
     "ieagan_ortho_ksplit": [],
     "ieagan_ortho_grad": [vp, vp, vp, vp, i, vp, i, vp, l, f, vp],
     "ieagan_selftest_tr_read": [vp, vp, vp],

@@ -100,15 +100,17 @@ def test(G, D, G_ema, state_dict, config, test_log):
     test_log.log(itr=int(state_dict["itr"]), FID=float(FID))
 
 
-def generated_statistics(net, config, n_events):
+def generated_statistics(net, config, n_events, clusters=False):
     """``utils.PXDStatistics`` over ``n_events`` events generated by ``net`` (eval mode when ``G_eval_mode``, no_grad, export epilogue).
     The latents and ``rdof`` come from a ``torch.Generator`` of its own seeded with ``config['seed']``: the global generators are not
-    touched; the ``.training`` flags are restored.  No host synchronisation."""
+    touched; the ``.training`` flags are restored.  No host synchronisation.  ``clusters=True``: the same events also go through a
+    ``utils.PXDClusterStatistics`` and ``(statistics, cluster statistics)`` is returned."""
     dev = next(net.parameters()).device
     n = int(config["n_classes"])
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(config["seed"]))
     stats = utils.PXDStatistics(n_sensors=n, threshold=float(config["val_threshold"]), device=dev)
+    cstats = utils.PXDClusterStatistics(n_sensors=n, threshold=float(config["val_threshold"]), device=dev) if clusters else None
     y = torch.arange(n, dtype=torch.long, device=dev)
     was_training = net.training
     if config["G_eval_mode"]:
@@ -118,10 +120,13 @@ def generated_statistics(net, config, n_events):
             for _ in range(n_events):
                 z = torch.randn(n, net.dim_z, generator=gen, device=dev)
                 rdof = torch.randn(n, net.rdof_dim, generator=gen, device=dev)
-                stats.update(net(z, y, rdof=rdof, export=True))
+                x = net(z, y, rdof=rdof, export=True)
+                stats.update(x)
+                if clusters:
+                    cstats.update(x)
     finally:
         net.train(was_training)
-    return stats
+    return (stats, cstats) if clusters else stats
 
 
 def validate(G, G_ema, real_stats, state_dict, config, log=None):

@@ -483,6 +483,155 @@ def pxd_digits(images, threshold=0.0, capacity=None, n_sensors=40):
     return PXDDigits(x, float(threshold), capacity, int(n_sensors), header, index, charge)
 
 
+# ---------------------------------------------------------------------------------------------------------
+# detector-level validation, cluster level: connected components of the digits and their spectra (csrc/pxd_clusters.hip)
+# ---------------------------------------------------------------------------------------------------------
+class PXDClusters:
+    """Device-side result of ``pxd_clusters``: the ``PXDDigits`` it was built from (``digits``), ``label`` int32 ``[capacity]`` (cluster
+    number of digit k) and the cluster table ``first`` / ``size`` / ``charge`` / ``size_u`` / ``size_v`` int32 and ``seed`` uint8, all
+    ``[capacity]`` (a batch has at most as many clusters as digits), ``counts`` int32 ``[N]`` (clusters per image), ``total`` int32
+    ``[1]``.  Only the first ``min(digits.total, capacity)`` labels and the first ``total`` table rows are written."""
+
+    def __init__(self, digits, label, first, size, charge, seed, size_u, size_v, header):
+        self.digits, self.capacity, self.n_sensors, self.shape = digits, digits.capacity, digits.n_sensors, digits.shape
+        self.label, self.first, self.size, self.charge, self.seed, self.size_u, self.size_v = label, first, size, charge, seed, size_u, size_v
+        self.header = header
+        self.counts, self.total = header[:self.shape[0]], header[self.shape[0]:]
+
+    def cpu(self):
+        """One read-back (every array packed into one device tensor, one copy, one wait) -> dict of NumPy arrays trimmed to the true
+        totals: per digit ``index``, ``digit_charge``, ``label``; per cluster ``first``, ``size``, ``charge``, ``seed``, ``size_u``,
+        ``size_v``, ``sensor`` (``first // (H*W) % n_sensors``), ``event``; ``counts [N]``, ``digit_counts [N]``.  Never truncated: when
+        the digit total exceeds the capacity, digits and clusters are run again with ``capacity = total`` (a second read-back, on that
+        path only)."""
+        N, Hh, Ww = self.shape
+        d = self.digits
+        i32 = lambda t: t.to(torch.int32)
+        packed = torch.cat([d.header, self.header, d.index, self.label, self.first, self.size, self.charge, self.size_u, self.size_v,
+                            i32(d.charge), i32(self.seed)]).cpu().numpy()
+        dcounts, dtotal = packed[:N].copy(), int(packed[N])
+        counts, total = packed[N + 1:2 * N + 1].copy(), int(packed[2 * N + 1])
+        if dtotal > self.capacity:
+            full = pxd_clusters(d.images, d.threshold, capacity=dtotal, n_sensors=self.n_sensors)
+            for k in ("digits", "capacity", "label", "first", "size", "charge", "seed", "size_u", "size_v", "header", "counts", "total"):
+                setattr(self, k, getattr(full, k))
+            return full.cpu()
+        C = self.capacity
+        col = lambda k, m: packed[2 * N + 2 + k * C:2 * N + 2 + k * C + m].copy()
+        first = col(2, total)
+        image = first // np.int32(Hh * Ww)
+        return dict(index=col(0, dtotal), label=col(1, dtotal), first=first, size=col(3, total), charge=col(4, total), size_u=col(5, total),
+                    size_v=col(6, total), digit_charge=col(7, dtotal).astype(np.uint8), seed=col(8, total).astype(np.uint8),
+                    sensor=(image % self.n_sensors).astype(np.int32), event=(image // self.n_sensors).astype(np.int32), counts=counts,
+                    digit_counts=dcounts)
+
+
+def pxd_clusters(images_or_digits, threshold=0.0, capacity=None, n_sensors=40):
+    """Clusters of a batch of sensor images ``[N, H, W]`` (fp32 or uint8 device tensor: ``pxd_digits(images, threshold, capacity,
+    n_sensors)`` runs first) or of an existing ``PXDDigits`` (its threshold, capacity and sensors hold): connected components of the
+    digits under 8-connectivity inside an image, numbered by the flat index of their first digit -- the raster numbering of
+    ``scipy.ndimage.label(img > 0, ones((3, 3)))`` per image with a running offset -- with size, summed charge, seed charge and row /
+    column extent per cluster, all integers, bit-identical run to run (csrc/pxd_clusters.hip).
+
+    Launches on the current stream, neither synchronises nor copies; with ``capacity`` given it can be captured into a HIP graph.  When
+    the digit total exceeds the capacity the device result covers the first ``capacity`` digits; ``PXDClusters.cpu()`` reruns instead
+    of handing back a truncated event."""
+    H.require_gpu()
+    d = images_or_digits if isinstance(images_or_digits, PXDDigits) else pxd_digits(images_or_digits, threshold, capacity, n_sensors)
+    N, Hh, Ww = d.shape
+    if Hh * Ww * 255 >= 2 ** 31:
+        raise ValueError(f"pxd_clusters: {Hh} x {Ww} pixels x 255 do not fit the int32 cluster charge")
+    dev, C = d.index.device, d.capacity
+    i32 = lambda: torch.empty(C, dtype=torch.int32, device=dev)
+    label, first, size, charge, size_u, size_v = i32(), i32(), i32(), i32(), i32(), i32()
+    seed = torch.empty(C, dtype=torch.uint8, device=dev)
+    header = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(H.lib().ieagan_pxd_clusters_scratch(N, Hh, Ww, C), dtype=torch.int32, device=dev)
+    p = (lambda t: t.data_ptr()) if C else (lambda t: None)
+    with torch.cuda.device(dev):
+        H.call("ieagan_pxd_clusters", p(d.index), p(d.charge), d.total.data_ptr(), N, Hh, Ww, C, p(label), p(first), p(size), p(charge),
+               p(seed), p(size_u), p(size_v), header.data_ptr(), header.data_ptr() + 4 * N, scratch.data_ptr(), H.stream())
+    return PXDClusters(d, label, first, size, charge, seed, size_u, size_v, header)
+
+
+class PXDClusterStatistics:
+    """Accumulator of per-sensor cluster spectra over batches of sensor images in detector units (``[N, H, W]`` fp32 or uint8, image ``n``
+    is sensor ``n % n_sensors``), beside ``PXDStatistics``: ``update`` runs digits -> clusters -> ``ieagan_pxd_cluster_stats`` on the
+    current stream and neither synchronises nor copies; ``result()`` does the single read-back.  Counters are exact int64.
+    ``capacity`` (digits per update) defaults to that of ``pxd_digits``; an update whose digit total exceeds it is counted on the device
+    and makes ``result()`` raise: a truncated event is never reported."""
+
+    def __init__(self, n_sensors=40, threshold=7.0, capacity=None, device=None):
+        self.n_sensors, self.threshold = int(n_sensors), float(threshold)
+        self.capacity = None if capacity is None else int(capacity)
+        self.device = torch.device(device) if device is not None else None
+        self.reset()
+
+    def reset(self):
+        self.tables = None              # int64 [S * 640 + 1] on the device: the spectra, then the overflow counter
+        self.clusters, self.shape = [], None
+
+    def update(self, images):
+        H.require_gpu()
+        if images.dim() == 4 and images.shape[1] == 1:
+            images = images[:, 0]
+        if self.device is None:
+            self.device = images.device if images.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        if images.dim() == 3 and self.shape is not None and self.shape != tuple(images.shape[1:]):
+            raise ValueError(f"PXDClusterStatistics.update: image size {tuple(images.shape[1:])} differs from the accumulated {self.shape}")
+        c = pxd_clusters(images.to(self.device, non_blocking=True), self.threshold, self.capacity, self.n_sensors)
+        N, Hh, Ww = c.shape
+        self.shape = (Hh, Ww)
+        S = self.n_sensors
+        if self.tables is None:
+            self.tables = torch.zeros(S * H.PXD_CLUSTER_BINS + 1, dtype=torch.int64, device=self.device)
+        p = (lambda t: t.data_ptr()) if c.capacity else (lambda t: None)
+        with torch.cuda.device(self.device):
+            H.call("ieagan_pxd_cluster_stats", p(c.first), p(c.size), p(c.charge), p(c.seed), p(c.size_u), p(c.size_v), c.total.data_ptr(),
+                   c.digits.total.data_ptr(), N, Hh, Ww, S, c.capacity, self.tables.data_ptr(),
+                   self.tables.data_ptr() + 8 * S * H.PXD_CLUSTER_BINS, H.stream())
+        self.clusters.append(c.counts)
+        return c
+
+    def result(self):
+        """NumPy tables: int64 ``size_spectrum [S, 64]`` (bin ``min(size, 64) - 1``), ``charge_spectrum [S, 256]`` (bin
+        ``min(charge >> 3, 255)``, 8 ADU a bin), ``seed_spectrum [S, 256]``, ``size_u_spectrum`` / ``size_v_spectrum [S, 32]`` (bin
+        ``min(s, 32) - 1``), ``clusters`` int32 ``[events, S]`` (clusters per image) and ``n_events``.  Raises when an update overflowed."""
+        if not self.clusters:
+            raise RuntimeError("PXDClusterStatistics.result() before any update()")
+        S, B = self.n_sensors, H.PXD_CLUSTER_BINS
+        packed = torch.cat([self.tables, torch.cat(self.clusters).to(torch.int64)]).cpu().numpy()      # the one device-to-host copy
+        overflow = int(packed[S * B])
+        if overflow != 0:
+            raise RuntimeError(f"PXDClusterStatistics: {overflow} update(s) held more digits than the capacity"
+                               f"{'' if self.capacity is None else ' of %d' % self.capacity}, their clusters are truncated: "
+                               "pass a larger capacity= to PXDClusterStatistics")
+        rows = packed[:S * B].reshape(S, B)
+        out = {k: rows[:, a:a + n].copy() for k, (a, n) in H.PXD_CLUSTER_COLUMNS.items()}
+        out["clusters"] = packed[S * B + 1:].astype(np.int32).reshape(-1, S)
+        out["n_events"] = int(out["clusters"].shape[0])
+        return out
+
+
+def pxd_cluster_distance(real, fake):
+    """Four distances between two ``PXDClusterStatistics.result()`` tables (float64, host): ``cluster_rate_rel_err`` = mean over the
+    sensors with real clusters of |fake - real| / real of the mean clusters per image; ``size_w1`` (pixels), ``cluster_charge_w1`` (ADU,
+    bins of 8) and ``seed_w1`` (ADU) = 1-D Wasserstein distances between the spectra pooled over the sensors and normalised to 1 (the
+    construction of ``pxd_distance`` for the ADC spectrum), NaN when one side has no cluster at all."""
+    r = np.asarray(real["clusters"], np.float64).mean(0)
+    f = np.asarray(fake["clusters"], np.float64).mean(0)
+    ok = r > 0
+    out = dict(cluster_rate_rel_err=float(np.mean(np.abs(f[ok] - r[ok]) / r[ok])) if ok.any() else float("nan"))
+    for name, key, width in (("size_w1", "size_spectrum", 1.0), ("cluster_charge_w1", "charge_spectrum", 8.0), ("seed_w1", "seed_spectrum", 1.0)):
+        hr = np.asarray(real[key], np.float64).sum(0)
+        hf = np.asarray(fake[key], np.float64).sum(0)
+        if hr.sum() > 0 and hf.sum() > 0:
+            out[name] = float(np.abs(np.cumsum(hf / hf.sum()) - np.cumsum(hr / hr.sum())).sum() * width)
+        else:
+            out[name] = float("nan")
+    return out
+
+
 def write_digits(path, event_offsets, sensor, ucell, vcell, charge):
     """The event file of ``produce.py`` (``.npz``): ``event_offsets`` int64 ``[events + 1]`` (the digits of event ``e`` are
     ``[event_offsets[e], event_offsets[e + 1])``), ``sensor`` uint8, ``ucell`` uint8, ``vcell`` uint16, ``charge`` uint8."""

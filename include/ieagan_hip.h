@@ -422,6 +422,35 @@ long ieagan_pxd_digits_scratch(int N, int H, int W);
 int ieagan_pxd_digits(const void* images, int is_u8, int N, int H, int W, float threshold, long capacity,
                       int* index, unsigned char* charge, int* counts, int* total, int* scratch, void* stream);
 
+/* ---- detector-level validation, cluster level (pxd_clusters.hip) -------------------------------------
+ * Connected components of the digits of ieagan_pxd_digits (index ascending, uint8 charge; digit_total = its `total`, read on the device)
+ * of a batch [N, H, W], N * H * W < 2^31 and H * W * 255 < 2^31.  Two digits are neighbours iff they lie in the same image and
+ * |dr| <= 1 && |dc| <= 1 (8-connectivity; never across an image boundary, never from column W-1 to column 0 of the next row).  Clusters
+ * are numbered 0, 1, ... by the flat index of their first (smallest) digit: the raster numbering of
+ * scipy.ndimage.label(img > 0, ones((3, 3))) per image with a running offset.  With M = min(*digit_total, capacity) digits and T clusters:
+ *   label [M] int32    cluster number of digit k
+ *   first [T] int32    flat index of the first digit          size [T] int32      number of digits
+ *   ccharge [T] int32  sum of the charges                     seed [T] uint8      largest charge
+ *   size_u [T], size_v [T] int32   row / column extent, max - min + 1
+ *   counts [N] int32   clusters per image (by `first`)        total [1] int32     T
+ * Every array except counts / total is [capacity] (T <= M <= capacity); nothing is written outside [0, M) of label and [0, T) of the
+ * tables.  When *digit_total > capacity the FIRST capacity digits are clustered (the caller compares digit_total with its capacity).
+ * Union-find with integer atomics only; the root of a cluster is its first digit whatever the schedule, no atomic decides a position:
+ * two calls on the same digits write the same bytes.  No workgroup waits on another, no synchronise, no copy (graph-capturable).
+ * scratch: ieagan_pxd_clusters_scratch(N, H, W, capacity) int32 words, need not be zeroed. */
+long ieagan_pxd_clusters_scratch(int N, int H, int W, long capacity);
+int ieagan_pxd_clusters(const int* index, const unsigned char* charge, const int* digit_total, int N, int H, int W, long capacity,
+                        int* label, int* first, int* size, int* ccharge, unsigned char* seed, int* size_u, int* size_v, int* counts,
+                        int* total, int* scratch, void* stream);
+/* Cluster spectra of one ieagan_pxd_clusters result, ACCUMULATED across calls (the caller zeroes them once): the cluster with first
+ * digit in image n counts for sensor n % n_sensors (N a multiple of n_sensors).  tables [n_sensors][640] 64-bit unsigned counters, the
+ * columns of a row:   0 ..  63  size, bin min(size, 64) - 1          64 .. 319  charge, bin min(charge >> 3, 255) (8 ADU a bin)
+ *                   320 .. 575  seed, bin seed                       576 .. 607 / 608 .. 639  size_u / size_v, bin min(s, 32) - 1
+ * overflow [1] 64-bit unsigned: incremented when *digit_total > capacity, i.e. when the clusters come from a truncated digit list. */
+int ieagan_pxd_cluster_stats(const int* first, const int* size, const int* ccharge, const unsigned char* seed, const int* size_u,
+                             const int* size_v, const int* cluster_total, const int* digit_total, int N, int H, int W, int n_sensors,
+                             long capacity, unsigned long long* tables, unsigned long long* overflow, void* stream);
+
 /* ---- orthogonal regularisation (ortho.hip) -------------------------------------------------------
  * Replaces utils.ortho (reference utils/__init__.py:843-859) for ALL weight matrices of a network in one call:
  * grad[l] += 2*strength * ((W_l W_l^T) (.) (1 - I)) W_l, fp32, on the flat parameter / gradient arenas.
