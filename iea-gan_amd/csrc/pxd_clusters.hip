@@ -23,14 +23,10 @@
 //            Writes the cluster table at the rank and rank[k].  No atomic decides a position.
 //   label    label[k] = rank[parent[k]];  counts[n] = clusters whose first digit lies in image n (two lower_bounds over `first`).
 // Two calls on the same digits write the same bytes.
-#include <climits>
-
 #include "common.h"
 #include "pxd_common.h"
 
-#define CL_WAVES (PXD_THREADS / 64)
-#define CL_MAX_BLOCKS 1024          // 4 * CL_MAX_BLOCKS wave slots = 4 per thread of the scan workgroup
-#define CL_SCAN_THREADS 1024
+#define CL_MAX_BLOCKS 1024          // one tile of the scan (pxd_common.h): 4 * CL_MAX_BLOCKS wave slots = 4 per thread of its workgroup
 #define CL_ACC 7                    // per-root accumulators: size, charge, seed, row min, row max, column min, column max
 
 #define CL_SIZE_BINS 64
@@ -45,7 +41,7 @@ static inline int cl_blocks(long cap) {
     return (int)(b < 1 ? 1 : b);
 }
 static inline int cl_chunk(long cap, int B) {       // digits per wave, a multiple of 64
-    const long c = (cap + (long)B * CL_WAVES - 1) / ((long)B * CL_WAVES);
+    const long c = (cap + (long)B * PXD_WAVES - 1) / ((long)B * PXD_WAVES);
     return (int)((c + 63) / 64 * 64 < 64 ? 64 : (c + 63) / 64 * 64);
 }
 
@@ -79,6 +75,16 @@ __device__ __forceinline__ void cl_union(int* parent, int a, int b) {
     }
 }
 
+__device__ __forceinline__ int cl_lower_bound(const int* __restrict__ a, int n, int v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
 __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_init_kernel(const int* __restrict__ dtotal, int cap, int* __restrict__ parent,
                                                                         int* __restrict__ acc) {
     const int M = min(dtotal[0], cap);
@@ -99,16 +105,13 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_link_kernel(const in
     const int M = min(dtotal[0], cap);
     for (int k = blockIdx.x * PXD_THREADS + threadIdx.x; k < M; k += gridDim.x * PXD_THREADS) {
         const int idx = index[k];
-        const int rem = idx % HW, r = rem / W, c = rem - r * W;
+        int r, c;
+        pxd_row_col(idx, HW, W, r, c);
         if (c > 0 && k > 0 && index[k - 1] == idx - 1) cl_union(parent, k, k - 1);
         if (r == 0) continue;
         const int up = idx - W;                     // the pixel above: same image, row r - 1
-        int lo = k - W - 1 > 0 ? k - W - 1 : 0, hi = k;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (index[mid] < up - 1) lo = mid + 1;
-            else hi = mid;
-        }
+        int lo = k - W - 1 > 0 ? k - W - 1 : 0;
+        lo += cl_lower_bound(index + lo, k - lo, up - 1);
         for (int j = lo; j < k && j < lo + 3; ++j) {
             const int d = index[j] - up;            // -1, 0, 1: up-left, up, up-right; larger: no neighbour
             if (d > 1) break;
@@ -120,7 +123,7 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_link_kernel(const in
 __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_flatten_kernel(const int* __restrict__ index, const uint8_t* __restrict__ charge,
                                                                            const int* __restrict__ dtotal, int cap, int chunk, int HW, int W,
                                                                            int* parent, int* acc, int* __restrict__ slots) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * CL_WAVES + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
     const long M = min(dtotal[0], cap);
     const long k0 = (long)g * chunk;
     const long k1 = k0 + chunk < M ? k0 + chunk : M;
@@ -131,7 +134,8 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_flatten_kernel(const
         __hip_atomic_store(parent + k, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         roots += (int)(root == k);
         const int q = (int)charge[k];
-        const int rem = index[k] % HW, r = rem / W, c = rem - r * W;
+        int r, c;
+        pxd_row_col(index[k], HW, W, r, c);
         atomicAdd(acc + root, 1);
         atomicAdd(acc + (long)cap + root, q);
         atomicMax(acc + 2L * cap + root, q);
@@ -145,40 +149,10 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_flatten_kernel(const
     if (lane == 0) slots[g] = roots;
 }
 
-// Exclusive prefix sum over the wave slots in place; thread i owns the four slots of workgroup i of the flatten launch.
-__global__ __launch_bounds__(CL_SCAN_THREADS) void pxd_clusters_scan_kernel(int* __restrict__ slots, int groups, int* __restrict__ total) {
-    __shared__ int wsum[CL_SCAN_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int c[CL_WAVES] = {0, 0, 0, 0};
-    if (tid < groups) {
-#pragma unroll
-        for (int k = 0; k < CL_WAVES; ++k) c[k] = slots[tid * CL_WAVES + k];
-    }
-    const int mine = c[0] + c[1] + c[2] + c[3];
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < CL_SCAN_THREADS / 64; ++k) {
-        const int s = wsum[k];
-        before += k < wave ? s : 0;
-        all += s;
-    }
-    int run = before + incl - mine;
-    if (tid < groups) {
-#pragma unroll
-        for (int k = 0; k < CL_WAVES; ++k) {
-            slots[tid * CL_WAVES + k] = run;
-            run += c[k];
-        }
-    }
-    if (tid == 0) total[0] = all;
+// The prefix sum of pxd_common.h over the wave slots of the flatten launch (groups <= CL_MAX_BLOCKS: one tile); writes total.
+__global__ __launch_bounds__(PXD_SCAN_THREADS) void pxd_clusters_scan_kernel(int* __restrict__ slots, int groups, int* __restrict__ total) {
+    const int all = pxd_scan_slots(slots, groups);
+    if (threadIdx.x == 0) total[0] = all;
 }
 
 __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_compact_kernel(const int* __restrict__ index, const int* __restrict__ dtotal, int cap,
@@ -187,7 +161,7 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_compact_kernel(const
                                                                            int* __restrict__ first, int* __restrict__ size, int* __restrict__ ccharge,
                                                                            uint8_t* __restrict__ seed, int* __restrict__ size_u,
                                                                            int* __restrict__ size_v) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * CL_WAVES + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
     const long M = min(dtotal[0], cap);
     const long k0 = (long)g * chunk;
     const long k1 = k0 + chunk < M ? k0 + chunk : M;
@@ -210,16 +184,6 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_compact_kernel(const
         }
         run += __popcll(m);
     }
-}
-
-__device__ __forceinline__ int cl_lower_bound(const int* __restrict__ a, int n, int v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_label_kernel(const int* __restrict__ dtotal, int cap, const int* __restrict__ parent,
@@ -255,17 +219,15 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_cluster_stats_kernel(const in
 
 extern "C" long ieagan_pxd_clusters_scratch(int N, int H, int W, long capacity) {
     if (N <= 0 || H <= 0 || W <= 0 || capacity < 0) return 0;
-    const long cap = capacity > INT_MAX ? INT_MAX : capacity;
-    return (2L + CL_ACC) * cap + (long)CL_WAVES * cl_blocks(cap);
+    const long cap = pxd_cap(capacity);
+    return (2L + CL_ACC) * cap + (long)PXD_WAVES * cl_blocks(cap);
 }
 
 extern "C" int ieagan_pxd_clusters(const int* index, const unsigned char* charge, const int* digit_total, int N, int H, int W, long capacity,
                                    int* label, int* first, int* size, int* ccharge, unsigned char* seed, int* size_u, int* size_v, int* counts,
                                    int* total, int* scratch, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    CHECK_ARG(N > 0 && N <= 65535, "pxd_clusters: N = %d outside 1 .. 65535", N);
-    CHECK_ARG(H > 0 && W > 0, "pxd_clusters: bad image size %d x %d", H, W);
-    CHECK_ARG((double)N * H * W < 2147483648.0, "pxd_clusters: N * H * W = %d * %d * %d does not fit the int32 flat index", N, H, W);
+    if (int rc = pxd_check_geometry("pxd_clusters", N, H, W, true)) return rc;
     CHECK_ARG((double)H * W * 255.0 < 2147483648.0, "pxd_clusters: H * W * 255 = %d * %d * 255 does not fit the int32 cluster charge", H, W);
     CHECK_ARG(capacity >= 0, "pxd_clusters: capacity = %ld is negative", capacity);
     CHECK_ARG(digit_total != nullptr && ((uintptr_t)digit_total & 3u) == 0, "pxd_clusters: digit_total is NULL or misaligned");
@@ -279,7 +241,7 @@ extern "C" int ieagan_pxd_clusters(const int* index, const unsigned char* charge
               "pxd_clusters: counts / total is NULL or misaligned");
     CHECK_ARG(scratch != nullptr && ((uintptr_t)scratch & 3u) == 0,
               "pxd_clusters: scratch (ieagan_pxd_clusters_scratch int32 words) is NULL or misaligned");
-    const int cap = capacity > INT_MAX ? INT_MAX : (int)capacity;
+    const int cap = pxd_cap(capacity);
     const int HW = H * W;
     const int B = cl_blocks(cap), chunk = cl_chunk(cap, B);
     int* parent = scratch;
@@ -294,7 +256,7 @@ extern "C" int ieagan_pxd_clusters(const int* index, const unsigned char* charge
     hipLaunchKernelGGL(pxd_clusters_flatten_kernel, dim3(B), dim3(PXD_THREADS), 0, st, index, (const uint8_t*)charge, digit_total, cap, chunk, HW, W,
                        parent, acc, slots);
     CHECK_LAUNCH("pxd_clusters flatten");
-    hipLaunchKernelGGL(pxd_clusters_scan_kernel, dim3(1), dim3(CL_SCAN_THREADS), 0, st, slots, B, total);
+    hipLaunchKernelGGL(pxd_clusters_scan_kernel, dim3(1), dim3(PXD_SCAN_THREADS), 0, st, slots, B, total);
     CHECK_LAUNCH("pxd_clusters scan");
     hipLaunchKernelGGL(pxd_clusters_compact_kernel, dim3(B), dim3(PXD_THREADS), 0, st, index, digit_total, cap, chunk, (const int*)parent,
                        (const int*)acc, (const int*)slots, rank, first, size, ccharge, (uint8_t*)seed, size_u, size_v);
@@ -309,9 +271,7 @@ extern "C" int ieagan_pxd_cluster_stats(const int* first, const int* size, const
                                         const int* size_v, const int* cluster_total, const int* digit_total, int N, int H, int W, int n_sensors,
                                         long capacity, unsigned long long* tables, unsigned long long* overflow, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    CHECK_ARG(N > 0 && N <= 65535, "pxd_cluster_stats: N = %d outside 1 .. 65535", N);
-    CHECK_ARG(H > 0 && W > 0, "pxd_cluster_stats: bad image size %d x %d", H, W);
-    CHECK_ARG((double)N * H * W < 2147483648.0, "pxd_cluster_stats: N * H * W = %d * %d * %d does not fit the int32 flat index", N, H, W);
+    if (int rc = pxd_check_geometry("pxd_cluster_stats", N, H, W, true)) return rc;
     CHECK_ARG(n_sensors > 0 && N % n_sensors == 0, "pxd_cluster_stats: N = %d is not a multiple of n_sensors = %d", N, n_sensors);
     CHECK_ARG(capacity >= 0, "pxd_cluster_stats: capacity = %ld is negative", capacity);
     CHECK_ARG(capacity == 0 || (first != nullptr && size != nullptr && ccharge != nullptr && seed != nullptr && size_u != nullptr &&
@@ -319,7 +279,7 @@ extern "C" int ieagan_pxd_cluster_stats(const int* first, const int* size, const
     CHECK_ARG(cluster_total != nullptr && digit_total != nullptr, "pxd_cluster_stats: cluster_total / digit_total is NULL");
     CHECK_ARG(tables != nullptr && overflow != nullptr && (((uintptr_t)tables | (uintptr_t)overflow) & 7u) == 0,
               "pxd_cluster_stats: tables / overflow is NULL or not 8-byte aligned");
-    const int cap = capacity > INT_MAX ? INT_MAX : (int)capacity;
+    const int cap = pxd_cap(capacity);
     ProfScope prof("pxd_cluster_stats", 0.0, 0.0, st);
     hipLaunchKernelGGL(pxd_cluster_stats_kernel, dim3(cl_blocks(cap)), dim3(PXD_THREADS), 0, st, first, size, ccharge, (const uint8_t*)seed, size_u,
                        size_v, cluster_total, digit_total, cap, H * W, n_sensors, tables, overflow);

@@ -14,13 +14,8 @@
 //            is base[slot] + digits of the wave's earlier steps + digits of the lower lanes of this step (wave prefix sum) + digits
 //            of the lane's lower pixels.  Stores with rank >= capacity are dropped.
 // Every step of count and compact evaluates the same function of the same bytes, so the ranks fill [0, total) exactly once.
-#include <climits>
-
 #include "common.h"
 #include "pxd_common.h"
-
-#define PXD_WAVES (PXD_THREADS / 64)
-#define PXD_SCAN_THREADS 1024
 
 // V pixels at a 16-byte aligned address -> V / 4 dwords of packed charges, four pixels a dword in address order, 0 where the pixel
 // is no digit.  `one` is the same rule for a single pixel (scalar head and tail), charge in the low byte.
@@ -64,36 +59,19 @@ __device__ __forceinline__ int pxd_nz_bytes(unsigned w) {
     return (int)((w & 0xffu) != 0u) + (int)((w & 0xff00u) != 0u) + (int)((w & 0xff0000u) != 0u) + (int)((w >> 24) != 0u);
 }
 
-// The pixel range of one wave: [start, start + len) of image n, split into a scalar head up to the first 16-byte boundary, nvec
-// 16-byte vectors and a scalar tail -- any H x W and any image offset.  chunk is a multiple of 64 pixels, a wave's quarter of 16.
-template <typename T> struct WaveRange {
-    const T* base;
-    long start;
-    int head, nvec, tail0, len;
-    __device__ __forceinline__ WaveRange(const T* x, long HW, long chunk, int n, int p, int wave) {
-        constexpr int V = DigVec<T>::V;
-        const long sub = chunk / PXD_WAVES;
-        long s = (long)p * chunk + (long)wave * sub;
-        long l = HW - s;
-        if (l > sub) l = sub;
-        if (l < 0) l = 0;
-        if (s > HW) s = HW;
-        start = (long)n * HW + s;
-        base = x + start;
-        len = (int)l;
-        head = (int)(((16u - (unsigned)((uintptr_t)base & 15u)) & 15u) / sizeof(T));
-        if (head > len) head = len;
-        nvec = (len - head) / V;
-        tail0 = head + nvec * V;
-    }
-};
+// The pixel range of one wave: quarter `wave` of part p of image n.  chunk is a multiple of 64 pixels, a wave's quarter of 16.
+template <typename T> using WaveRange = PxdSpan<T, DigVec<T>::V, int>;
+template <typename T> __device__ __forceinline__ WaveRange<T> pxd_wave_range(const T* x, long HW, long chunk, int n, int p, int wave) {
+    const long sub = chunk / PXD_WAVES, s = (long)p * chunk + (long)wave * sub;
+    return WaveRange<T>(x + (long)n * HW + (s > HW ? HW : s), (int)pxd_clip(HW, s, sub));
+}
 
 template <typename T>
 __global__ __launch_bounds__(PXD_THREADS) void pxd_digits_count_kernel(const T* __restrict__ x, long HW, long chunk, float thr, unsigned tq,
                                                                        int* __restrict__ slots) {
     constexpr int V = DigVec<T>::V, W = DigVec<T>::W;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = blockIdx.y, p = blockIdx.x;
-    const WaveRange<T> r(x, HW, chunk, n, p, wave);
+    const WaveRange<T> r = pxd_wave_range(x, HW, chunk, n, p, wave);
     int c = 0;
     if (lane < r.head) c += (int)(DigVec<T>::one(r.base + lane, thr, tq) != 0u);      // head and tail are shorter than V <= 16 pixels
     for (int i = lane; i < r.nvec; i += 64) {
@@ -108,49 +86,14 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_digits_count_kernel(const T* 
     if (lane == 0) slots[((long)n * gridDim.x + p) * PXD_WAVES + wave] = c;
 }
 
-// Exclusive prefix sum over slots[groups][4] in place; thread i of a tile owns the four slots of workgroup i.
+// The prefix sum of pxd_common.h over the slots of the count launch; then counts[N] and total from the bases.
 __global__ __launch_bounds__(PXD_SCAN_THREADS) void pxd_digits_scan_kernel(int* __restrict__ slots, int groups, int N, int P,
                                                                            int* __restrict__ counts, int* __restrict__ total) {
-    __shared__ int wsum[PXD_SCAN_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int carry = 0;
-    for (int g0 = 0; g0 < groups; g0 += PXD_SCAN_THREADS) {
-        const int g = g0 + tid;
-        int c[PXD_WAVES] = {0, 0, 0, 0};
-        if (g < groups) {
-#pragma unroll
-            for (int k = 0; k < PXD_WAVES; ++k) c[k] = slots[(long)g * PXD_WAVES + k];
-        }
-        const int mine = c[0] + c[1] + c[2] + c[3];
-        int incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += y;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int before = 0, tile = 0;
-#pragma unroll
-        for (int k = 0; k < PXD_SCAN_THREADS / 64; ++k) {
-            const int s = wsum[k];
-            before += k < wave ? s : 0;
-            tile += s;
-        }
-        int run = carry + before + incl - mine;
-        if (g < groups) {
-#pragma unroll
-            for (int k = 0; k < PXD_WAVES; ++k) {
-                slots[(long)g * PXD_WAVES + k] = run;
-                run += c[k];
-            }
-        }
-        carry += tile;
-        __syncthreads();                    // wsum is rewritten by the next tile; the bases written above are visible to this workgroup
-    }
-    if (tid == 0) total[0] = carry;
+    const int tid = threadIdx.x;
+    const int all = pxd_scan_slots(slots, groups);
+    if (tid == 0) total[0] = all;
     for (int n = tid; n < N; n += PXD_SCAN_THREADS) {
-        const int end = n + 1 < N ? slots[(long)(n + 1) * P * PXD_WAVES] : carry;
+        const int end = n + 1 < N ? slots[(long)(n + 1) * P * PXD_WAVES] : all;
         counts[n] = end - slots[(long)n * P * PXD_WAVES];
     }
 }
@@ -163,12 +106,7 @@ __device__ __forceinline__ void pxd_wave_emit(const unsigned (&w)[W], int flat0,
 #pragma unroll
     for (int k = 0; k < W; ++k) c += pxd_nz_bytes(w[k]);
     if (__ballot(c > 0) == 0ull) return;            // wave-uniform: no digit in this step
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += y;
-    }
+    const int incl = pxd_wave_scan(c, lane);
     int k = run + incl - c;
     run += __shfl(incl, 63, 64);
 #pragma unroll
@@ -194,10 +132,10 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_digits_compact_kernel(const T
                                                                          uint8_t* __restrict__ charge) {
     constexpr int V = DigVec<T>::V, W = DigVec<T>::W;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = blockIdx.y, p = blockIdx.x;
-    const WaveRange<T> r(x, HW, chunk, n, p, wave);
+    const WaveRange<T> r = pxd_wave_range(x, HW, chunk, n, p, wave);
     int run = slots[((long)n * gridDim.x + p) * PXD_WAVES + wave];
     if (run >= cap) return;                         // wave-uniform: everything this wave would store is beyond the capacity
-    const int flat = (int)r.start;                  // N * H * W < 2^31 (checked by the launcher)
+    const int flat = (int)(r.base - x);             // N * H * W < 2^31 (checked by the launcher)
     {
         const unsigned one[1] = {lane < r.head ? DigVec<T>::one(r.base + lane, thr, tq) : 0u};
         pxd_wave_emit<1>(one, flat + lane, lane, run, cap, index, charge);
@@ -224,24 +162,19 @@ extern "C" long ieagan_pxd_digits_scratch(int N, int H, int W) {
 extern "C" int ieagan_pxd_digits(const void* images, int is_u8, int N, int H, int W, float threshold, long capacity, int* index,
                                  unsigned char* charge, int* counts, int* total, int* scratch, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    CHECK_ARG(images != nullptr, "pxd_digits: images is NULL");
-    CHECK_ARG(is_u8 == 0 || is_u8 == 1, "pxd_digits: is_u8 must be 0 (fp32) or 1 (uint8), got %d", is_u8);
-    CHECK_ARG(N > 0 && N <= 65535, "pxd_digits: N = %d outside 1 .. 65535", N);
-    CHECK_ARG(H > 0 && W > 0, "pxd_digits: bad image size %d x %d", H, W);
-    CHECK_ARG((double)N * H * W < 2147483648.0, "pxd_digits: N * H * W = %d * %d * %d does not fit the int32 flat index", N, H, W);
-    CHECK_ARG(threshold == threshold, "pxd_digits: threshold is NaN");
+    if (int rc = pxd_check_images("pxd_digits", images, is_u8, threshold)) return rc;
+    if (int rc = pxd_check_geometry("pxd_digits", N, H, W, true)) return rc;
     CHECK_ARG(capacity >= 0, "pxd_digits: capacity = %ld is negative", capacity);
     CHECK_ARG(capacity == 0 || (index != nullptr && charge != nullptr), "pxd_digits: index / charge is NULL with capacity %ld", capacity);
     CHECK_ARG(((uintptr_t)index & 3u) == 0, "pxd_digits: index is not 4-byte aligned");
     CHECK_ARG(counts != nullptr && total != nullptr && (((uintptr_t)counts | (uintptr_t)total) & 3u) == 0,
               "pxd_digits: counts / total is NULL or misaligned");
     CHECK_ARG(scratch != nullptr && ((uintptr_t)scratch & 3u) == 0, "pxd_digits: scratch (ieagan_pxd_digits_scratch int32 words) is NULL or misaligned");
-    CHECK_ARG(is_u8 || ((uintptr_t)images & 3u) == 0, "pxd_digits: fp32 images are not 4-byte aligned");
     const long HW = (long)H * W;
     const int P = pxd_parts(N, HW);
     long chunk = (HW + P - 1) / P;
     chunk = (chunk + 16 * PXD_WAVES - 1) / (16 * PXD_WAVES) * (16 * PXD_WAVES);
-    const int cap = capacity > INT_MAX ? INT_MAX : (int)capacity;
+    const int cap = pxd_cap(capacity);
     // uint8 input: v >= threshold <=> v >= ceil(threshold) in integers
     const float tc = ceilf(threshold);
     const unsigned tq = tc <= 0.f ? 0u : tc >= 256.f ? 256u : (unsigned)tc;
@@ -250,22 +183,12 @@ extern "C" int ieagan_pxd_digits(const void* images, int is_u8, int N, int H, in
     const double in_bytes = (double)N * HW * (is_u8 ? 1.0 : 4.0);
     const double bytes = 2.0 * in_bytes + 4.0 * 4.0 * PXD_WAVES * N * P + 4.0 * (N + 1);
     ProfScope prof(is_u8 ? "pxd_digits_u8" : "pxd_digits_f32", 0.0, bytes, st, nullptr, in_bytes);
-    if (is_u8)
-        hipLaunchKernelGGL(pxd_digits_count_kernel<uint8_t>, dim3(P, N), dim3(PXD_THREADS), 0, st, (const uint8_t*)images, HW, chunk, threshold, tq,
-                           scratch);
-    else
-        hipLaunchKernelGGL(pxd_digits_count_kernel<float>, dim3(P, N), dim3(PXD_THREADS), 0, st, (const float*)images, HW, chunk, threshold, tq,
-                           scratch);
+    PXD_LAUNCH(pxd_digits_count_kernel, is_u8, P, N, st, images, HW, chunk, threshold, tq, scratch);
     CHECK_LAUNCH("pxd_digits count");
     hipLaunchKernelGGL(pxd_digits_scan_kernel, dim3(1), dim3(PXD_SCAN_THREADS), 0, st, scratch, N * P, N, P, counts, total);
     CHECK_LAUNCH("pxd_digits scan");
     if (cap > 0) {
-        if (is_u8)
-            hipLaunchKernelGGL(pxd_digits_compact_kernel<uint8_t>, dim3(P, N), dim3(PXD_THREADS), 0, st, (const uint8_t*)images, HW, chunk,
-                               threshold, tq, (const int*)scratch, cap, index, charge);
-        else
-            hipLaunchKernelGGL(pxd_digits_compact_kernel<float>, dim3(P, N), dim3(PXD_THREADS), 0, st, (const float*)images, HW, chunk, threshold,
-                               tq, (const int*)scratch, cap, index, charge);
+        PXD_LAUNCH(pxd_digits_compact_kernel, is_u8, P, N, st, images, HW, chunk, threshold, tq, (const int*)scratch, cap, index, charge);
         CHECK_LAUNCH("pxd_digits compact");
     }
     return 0;

@@ -65,19 +65,11 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_stats_kernel(const T* __restr
     hist[tid] = 0u;
     __syncthreads();
     const long s = (long)p * chunk;
-    long len = HW - s;
-    if (len > chunk) len = chunk;
-    if (len < 0) len = 0;
-    const T* base = x + (long)n * HW + s;
-    // scalar head up to the first 16-byte boundary, 16-byte body, scalar tail: any H x W, any image offset
-    long head = (long)(((16u - (unsigned)((uintptr_t)base & 15u)) & 15u) / sizeof(T));
-    if (head > len) head = len;
-    const long nvec = (len - head) / V;
-    const long tail0 = head + nvec * V;
+    const PxdSpan<T, V, long> r(x + (long)n * HW + s, pxd_clip(HW, s, chunk));
     PxdAcc a = {0, 0.f};
-    if (tid < head) pxd_pixel((float)base[tid], threshold, hist, a);
-    for (long i = tid; i < nvec; i += PXD_THREADS) PxdVec<T>::run(base + head + i * V, threshold, hist, a);
-    if (tail0 + tid < len) pxd_pixel((float)base[tail0 + tid], threshold, hist, a);      // the tail is shorter than V <= 16 pixels
+    if (tid < r.head) pxd_pixel((float)r.base[tid], threshold, hist, a);
+    for (long i = tid; i < r.nvec; i += PXD_THREADS) PxdVec<T>::run(r.base + r.head + i * V, threshold, hist, a);
+    if (r.tail0 + tid < r.len) pxd_pixel((float)r.base[r.tail0 + tid], threshold, hist, a);
     // block totals in a fixed order: lanes (butterfly), then the four waves
     int h = a.hits;
     float c = a.charge;
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_stats_kernel(const T* __restr
     }
     if (tid < PXD_BINS) {
         unsigned long long cnt = hist[tid];
-        if (tid == 0) cnt += (unsigned long long)(len - bh);
+        if (tid == 0) cnt += (unsigned long long)(r.len - bh);
         if (cnt) atomicAdd(&spectrum[(long)(n % n_sensors) * PXD_BINS + tid], cnt);
     }
 }
@@ -130,16 +122,12 @@ extern "C" long ieagan_pxd_stats_scratch(int N, int H, int W) {
 extern "C" int ieagan_pxd_stats(const void* images, int is_u8, int N, int H, int W, int n_sensors, float threshold,
                                 unsigned long long* spectrum, int* hits, float* charge, float* scratch, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    CHECK_ARG(images != nullptr, "pxd_stats: images is NULL");
-    CHECK_ARG(is_u8 == 0 || is_u8 == 1, "pxd_stats: is_u8 must be 0 (fp32) or 1 (uint8), got %d", is_u8);
-    CHECK_ARG(N > 0 && N <= 65535, "pxd_stats: N = %d outside 1 .. 65535", N);
-    CHECK_ARG(H > 0 && W > 0, "pxd_stats: bad image size %d x %d", H, W);
+    if (int rc = pxd_check_images("pxd_stats", images, is_u8, threshold)) return rc;
+    if (int rc = pxd_check_geometry("pxd_stats", N, H, W, false)) return rc;
     CHECK_ARG(n_sensors > 0 && N % n_sensors == 0, "pxd_stats: N = %d is not a multiple of n_sensors = %d", N, n_sensors);
-    CHECK_ARG(threshold == threshold, "pxd_stats: threshold is NaN");
     CHECK_ARG(spectrum != nullptr && ((uintptr_t)spectrum & 7u) == 0, "pxd_stats: spectrum is NULL or not 8-byte aligned");
     CHECK_ARG(hits != nullptr && charge != nullptr, "pxd_stats: hits / charge is NULL");
     CHECK_ARG(scratch != nullptr && ((uintptr_t)scratch & 3u) == 0, "pxd_stats: scratch (ieagan_pxd_stats_scratch floats) is NULL or misaligned");
-    CHECK_ARG(is_u8 || ((uintptr_t)images & 3u) == 0, "pxd_stats: fp32 images are not 4-byte aligned");
     const long HW = (long)H * W;
     const int P = pxd_parts(N, HW);
     long chunk = (HW + P - 1) / P;
@@ -148,12 +136,7 @@ extern "C" int ieagan_pxd_stats(const void* images, int is_u8, int N, int H, int
     float* part_charge = scratch + (long)N * P;
     const double bytes = (double)N * HW * (is_u8 ? 1.0 : 4.0) + 16.0 * N * P + 8.0 * N;
     ProfScope prof(is_u8 ? "pxd_stats_u8" : "pxd_stats_f32", 0.0, bytes, st);
-    if (is_u8)
-        hipLaunchKernelGGL(pxd_stats_kernel<uint8_t>, dim3(P, N), dim3(PXD_THREADS), 0, st, (const uint8_t*)images, HW, chunk, n_sensors, threshold,
-                           spectrum, part_hits, part_charge);
-    else
-        hipLaunchKernelGGL(pxd_stats_kernel<float>, dim3(P, N), dim3(PXD_THREADS), 0, st, (const float*)images, HW, chunk, n_sensors, threshold,
-                           spectrum, part_hits, part_charge);
+    PXD_LAUNCH(pxd_stats_kernel, is_u8, P, N, st, images, HW, chunk, n_sensors, threshold, spectrum, part_hits, part_charge);
     CHECK_LAUNCH("pxd_stats");
     hipLaunchKernelGGL(pxd_fold_kernel, dim3(cdiv(N, 64)), dim3(64), 0, st, (const int*)part_hits, (const float*)part_charge, N, P, hits, charge);
     CHECK_LAUNCH("pxd_stats fold");

@@ -1,0 +1,405 @@
+"""The PXD detector surface, this project's own (no counterpart in the reference's ``utils``): detector-level validation statistics
+(csrc/pxd_stats.hip), event production as sparse digits (csrc/pxd_digits.hip), clusters of the digits and their spectra
+(csrc/pxd_clusters.hip) and the event file of ``produce.py``.  ``utils`` re-exports every name defined here."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+import _hip as H
+
+
+def _sensor_images(images, n_sensors, who, device=None):
+    """What every entry point does with its input: ``[N, H, W]`` (or ``[N, 1, H, W]``) fp32 or uint8 sensor images, whole events of
+    ``n_sensors``, as a contiguous tensor on ``device`` (default: the images' own GPU, the current one for host images)."""
+    H.require_gpu()
+    if images.dim() == 4 and images.shape[1] == 1:
+        images = images[:, 0]
+    if images.dim() != 3 or images.dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"{who} expects fp32 or uint8 sensor images [N, H, W] in detector units")
+    if images.shape[0] == 0 or images.shape[0] % n_sensors:
+        raise ValueError(f"{who}: {images.shape[0]} images are not whole events of {n_sensors} sensors")
+    if device is None:
+        device = images.device if images.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    return images.to(device, non_blocking=True).contiguous()
+
+
+def _ptrs(capacity, *tensors):
+    """Device pointers of ``tensors`` for a launcher; None each when the capacity is 0 (nothing is written then, NULL is accepted)."""
+    return [t.data_ptr() if capacity else None for t in tensors]
+
+
+def _rel_err(real, fake, ok):
+    """Mean over the sensors ``ok`` of |fake - real| / real (a NaN of ``fake`` counts as 0); NaN when there is no such sensor."""
+    r, f = np.asarray(real, np.float64), np.nan_to_num(np.asarray(fake, np.float64), nan=0.0)
+    return float(np.mean(np.abs(f[ok] - r[ok]) / r[ok])) if ok.any() else float("nan")
+
+
+def _w1(real_hist, fake_hist, width=1.0):
+    """1-D Wasserstein distance between two spectra ``[S, bins]``, bins ``width`` wide, pooled over the sensors, normalised; NaN if one is empty."""
+    hr = np.asarray(real_hist, np.float64).sum(0)
+    hf = np.asarray(fake_hist, np.float64).sum(0)
+    if hr.sum() > 0 and hf.sum() > 0:
+        return float(np.abs(np.cumsum(hf / hf.sum()) - np.cumsum(hr / hr.sum())).sum() * width)
+    return float("nan")
+
+# ---------------------------------------------------------------------------------------------------------
+# detector-level validation (reference Evaluation/eval_all.py:75-120): per-sensor occupancy, mean hit charge, ADC spectrum
+# ---------------------------------------------------------------------------------------------------------
+PXD_OCC_BINS = 200          # eval_all.py:78: bh.axis.Regular(200, 0, 0.02) over the per-image occupancy
+
+
+def pxd_bin_edges():
+    """The 252 edges of the 251 ADC-spectrum bins (eval_all.py:77): [-1, 1, 7, 8, 9, ..., 256]."""
+    return np.concatenate([np.array([-1.0, 1.0, 7.0]), np.linspace(8, 256, 249)])
+
+
+def pxd_bin_index(v):
+    """The bin rule of ``ieagan_pxd_stats`` restated on the host: ``v < 1 -> 0; v < 7 -> 1; else 2 + min(floor(v) - 7, 248)``.
+    Equals ``np.histogram(v, pxd_bin_edges())`` for every v in [-1, 256]."""
+    v = np.asarray(v, dtype=np.float64)
+    return np.where(v < 1, 0, np.where(v < 7, 1, 2 + np.minimum(np.floor(np.minimum(v, 255.0)) - 7, 248))).astype(np.int64)
+
+
+class PXDStatistics:
+    """Accumulator of the reference's per-event detector statistics (eval_all.py:75-101 ``get_stats``) over batches of sensor images in
+    detector units, ``[N, H, W]`` fp32 (``Generator(..., export=True)``) or uint8 (event files); image ``n`` is sensor
+    ``n % n_sensors``.  ``update`` is one HIP launch pair (csrc/pxd_stats.hip) on the current stream: it neither synchronises nor
+    copies to the host; ``result()`` does the single read-back."""
+
+    def __init__(self, n_sensors=40, threshold=7.0, device=None):
+        self.n_sensors, self.threshold = int(n_sensors), float(threshold)
+        self.device = torch.device(device) if device is not None else None
+        self.reset()
+
+    def reset(self):
+        self.spectrum = None            # int64 [S, 251] on the device (the kernel's 64-bit unsigned counters)
+        self.hits, self.charge, self.shape = [], [], None
+
+    def update(self, images):
+        x = _sensor_images(images, self.n_sensors, "PXDStatistics.update", self.device)
+        self.device = self.device or x.device
+        if self.shape not in (None, tuple(x.shape[1:])):
+            raise ValueError(f"PXDStatistics.update: image size {tuple(x.shape[1:])} differs from the accumulated {self.shape}")
+        self.shape = tuple(x.shape[1:])
+        N, Hh, Ww = x.shape
+        if self.spectrum is None:
+            self.spectrum = torch.zeros(self.n_sensors, H.PXD_BINS, dtype=torch.int64, device=self.device)
+        hits = torch.empty(N, dtype=torch.int32, device=self.device)
+        charge = torch.empty(N, dtype=torch.float32, device=self.device)
+        scratch = torch.empty(H.lib().ieagan_pxd_stats_scratch(N, Hh, Ww), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            H.call("ieagan_pxd_stats", x.data_ptr(), int(x.dtype == torch.uint8), N, Hh, Ww, self.n_sensors, self.threshold,
+                   self.spectrum.data_ptr(), hits.data_ptr(), charge.data_ptr(), scratch.data_ptr(), H.stream())
+        self.hits.append(hits)
+        self.charge.append(charge)
+        return hits, charge
+
+    def result(self):
+        """NumPy tables: ``spectrum [S, 251]``, ``occupancy [S]`` (mean over events of hits / (H*W)), ``mean_charge [S]`` (mean over
+        the events in which the sensor had a hit of charge / hits; NaN for a sensor that never had one), ``occ_hist [200]`` over
+        [0, 0.02) of every per-image occupancy plus ``occ_overflow``, ``n_events``; and the per-image ``hits`` / ``charge`` ``[E, S]``.
+        The occupancy bin is ``(hits * 10000) // (H*W)`` in integers: a bin edge of ``linspace(0, 0.02, 201)`` is then decided
+        exactly, not by float rounding."""
+        if not self.hits:
+            raise RuntimeError("PXDStatistics.result() before any update()")
+        S = self.n_sensors
+        px = self.shape[0] * self.shape[1]
+        packed = torch.cat([self.spectrum.reshape(-1), torch.cat(self.hits).to(torch.int64),
+                            torch.cat(self.charge).view(torch.int32).to(torch.int64)]).cpu().numpy()      # the one device-to-host copy
+        spectrum = packed[:S * H.PXD_BINS].reshape(S, H.PXD_BINS).copy()
+        n = (packed.size - S * H.PXD_BINS) // 2
+        hits = packed[S * H.PXD_BINS:S * H.PXD_BINS + n].reshape(-1, S)
+        charge = packed[S * H.PXD_BINS + n:].astype(np.int32).view(np.float32).reshape(-1, S)
+        occupancy = (hits.astype(np.float64) / px).mean(0)
+        has = hits > 0
+        per = np.where(has, charge.astype(np.float64) / np.maximum(hits, 1), 0.0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean_charge = per.sum(0) / has.sum(0)
+        b = (hits.reshape(-1) * 10000) // px
+        occ_hist = np.bincount(b[b < PXD_OCC_BINS], minlength=PXD_OCC_BINS).astype(np.int64)
+        return dict(spectrum=spectrum, occupancy=occupancy, mean_charge=mean_charge, occ_hist=occ_hist,
+                    occ_overflow=int((b >= PXD_OCC_BINS).sum()), n_events=int(hits.shape[0]), hits=hits.copy(), charge=charge.copy())
+
+
+def pxd_distance(real, fake):
+    """Three distances between two ``PXDStatistics.result()`` tables (float64, host): ``occ_rel_err`` / ``charge_rel_err`` = mean over
+    the sensors with real occupancy > 0 of |fake - real| / real (a fake sensor that never had a hit counts with mean charge 0, i.e.
+    a relative error of 1); ``spectrum_w1`` = the 1-D Wasserstein distance in ADU between the hit spectra (bins 2 .. 250, one ADU
+    wide, pooled over the sensors, each normalised to 1), NaN when one side has no hit at all."""
+    occ_r = np.asarray(real["occupancy"], np.float64)
+    return dict(occ_rel_err=_rel_err(occ_r, fake["occupancy"], occ_r > 0),
+                charge_rel_err=_rel_err(real["mean_charge"], fake["mean_charge"], occ_r > 0),
+                spectrum_w1=_w1(np.asarray(real["spectrum"])[:, 2:], np.asarray(fake["spectrum"])[:, 2:]))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# event production (reference Physics_Analysis/create_g1.py:62-79): sparse digits (sensor, u cell, v cell, charge)
+# ---------------------------------------------------------------------------------------------------------
+PXD_DIGITS_FRACTION = 16    # default capacity of pxd_digits: one digit per 16 pixels (6.25 %; PXD background sits near 1 %)
+
+
+class PXDDigits:
+    """Device-side result of ``pxd_digits``: ``index`` int32 ``[capacity]`` (flat position ``n*H*W + r*W + c``, ascending), ``charge``
+    uint8 ``[capacity]``, ``counts`` int32 ``[N]``, ``total`` int32 ``[1]`` -- only the first ``min(total, capacity)`` digits are
+    written.  ``start_copy`` enqueues the device-to-host copies, ``cpu()`` / ``unpack()`` wait for them (one wait)."""
+
+    def __init__(self, images, threshold, capacity, n_sensors, header, index, charge):
+        self.images, self.threshold, self.capacity, self.n_sensors = images, threshold, capacity, n_sensors
+        self.shape = tuple(images.shape)
+        self.header, self.index, self.charge = header, index, charge
+        self.counts, self.total = header[:self.shape[0]], header[self.shape[0]:]
+        self._host = None
+
+    def start_copy(self, expect=None, buffers=None):
+        """Enqueue the copy of the header (``counts``, ``total``) and of the first ``expect`` digits (default: ``capacity``) into
+        pinned host memory on the current stream, and record an event; does not wait.  ``buffers``: pinned tensors
+        ``(header int32 [>= N+1], index int32, charge uint8)`` to reuse instead of allocating."""
+        m = self.capacity if expect is None else max(0, min(int(expect), self.capacity))
+        N = self.shape[0]
+        if buffers is None:
+            buffers = (torch.empty(N + 1, dtype=torch.int32, pin_memory=True), torch.empty(m, dtype=torch.int32, pin_memory=True),
+                       torch.empty(m, dtype=torch.uint8, pin_memory=True))
+        hdr, idx, chg = buffers
+        if hdr.numel() < N + 1 or idx.numel() < m or chg.numel() < m:
+            raise ValueError("PXDDigits.start_copy: a host buffer is too short")
+        with torch.cuda.device(self.header.device):
+            hdr[:N + 1].copy_(self.header, non_blocking=True)
+            idx[:m].copy_(self.index[:m], non_blocking=True)
+            chg[:m].copy_(self.charge[:m], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self._host = (hdr, idx, chg, m, ev)
+        return self
+
+    def cpu(self):
+        """NumPy ``(index [total], charge [total], counts [N])``: waits once for the copies of ``start_copy`` (started here when the
+        caller did not).  Never truncated: when ``total`` exceeds the capacity the kernel is run again with ``capacity = total``, and
+        when it exceeds what was copied the rest is copied -- a second wait, on those paths only."""
+        if self._host is None:
+            self.start_copy()
+        hdr, idx, chg, m, ev = self._host
+        ev.synchronize()
+        N = self.shape[0]
+        counts, total = hdr[:N].numpy().copy(), int(hdr[N])
+        if total > self.capacity:
+            full = pxd_digits(self.images, self.threshold, capacity=total, n_sensors=self.n_sensors)
+            self.capacity, self.header, self.index, self.charge = total, full.header, full.index, full.charge
+            self.counts, self.total = full.counts, full.total
+            return self.index.cpu().numpy(), self.charge.cpu().numpy(), counts
+        index, charge = idx[:min(m, total)].numpy().copy(), chg[:min(m, total)].numpy().copy()
+        if total > m:
+            index = np.concatenate([index, self.index[m:total].cpu().numpy()])
+            charge = np.concatenate([charge, self.charge[m:total].cpu().numpy()])
+        return index, charge, counts
+
+    def unpack(self):
+        """NumPy ``(event, sensor, ucell, vcell, charge)`` of every digit, in ascending flat index: image ``n`` is sensor
+        ``n % n_sensors`` of event ``n // n_sensors``, ``ucell`` the row and ``vcell`` the column (create_g1.py:77, :106)."""
+        index, charge, _ = self.cpu()
+        return unpack_digits(index, charge, self.shape, self.n_sensors)
+
+
+def unpack_digits(index, charge, shape, n_sensors=40):
+    """Flat digit positions of an ``[N, H, W]`` batch -> ``(event, sensor, ucell, vcell, charge)`` arrays."""
+    N, Hh, Ww = shape
+    index = np.asarray(index)
+    if index.dtype != np.int32:                 # the kernel's own int32 positions are split in int32 (N*H*W < 2^31)
+        index = index.astype(np.int64)
+    n, rest = np.divmod(index, index.dtype.type(Hh * Ww))
+    r, c = np.divmod(rest, index.dtype.type(Ww))
+    return ((n // n_sensors).astype(np.int32), (n % n_sensors).astype(np.uint8 if n_sensors <= 256 else np.int32),
+            r.astype(np.uint8 if Hh <= 256 else np.uint16), c.astype(np.uint16), np.asarray(charge, np.uint8))
+
+
+def pxd_digits(images, threshold=0.0, capacity=None, n_sensors=40):
+    """Sparse digits of a batch of sensor images in detector units, ``[N, H, W]`` fp32 (``Generator(..., export=True)``) or uint8 (event
+    files), compacted on the device (csrc/pxd_digits.hip): the reference's ``.to(uint8)`` / ``nonzero()`` / gather
+    (Physics_Analysis/create_g1.py:73-79) without the dense tensor crossing PCIe.  A pixel is a digit iff its truncated charge
+    ``q = uint8(min(max(v, 0), 255))`` is positive and ``v >= threshold`` (0: the reference's production behaviour, 7: the evaluation
+    cut); digits come in ascending flat index, the order of ``torch.nonzero``, bit-identical run to run.
+
+    Launches on the current stream, neither synchronises nor copies; with ``capacity`` given it can be captured into a HIP graph.
+    ``capacity`` (digits) defaults to one per 16 pixels (``N*H*W // 16``, at least 1024).  ``counts`` and ``total`` of the returned
+    ``PXDDigits`` always hold the true numbers; its ``cpu()`` / ``unpack()`` rerun with a larger capacity instead of truncating."""
+    x = _sensor_images(images, n_sensors, "pxd_digits")
+    dev = x.device
+    N, Hh, Ww = x.shape
+    if N * Hh * Ww >= 2 ** 31:
+        raise ValueError(f"pxd_digits: {N} x {Hh} x {Ww} pixels do not fit the int32 flat index; split the batch")
+    capacity = max(1024, N * Hh * Ww // PXD_DIGITS_FRACTION) if capacity is None else int(capacity)
+    if capacity < 0:
+        raise ValueError("pxd_digits: capacity is negative")
+    header = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    index = torch.empty(capacity, dtype=torch.int32, device=dev)
+    charge = torch.empty(capacity, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(H.lib().ieagan_pxd_digits_scratch(N, Hh, Ww), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        H.call("ieagan_pxd_digits", x.data_ptr(), int(x.dtype == torch.uint8), N, Hh, Ww, float(threshold), capacity,
+               *_ptrs(capacity, index, charge), header.data_ptr(), header.data_ptr() + 4 * N, scratch.data_ptr(), H.stream())
+    return PXDDigits(x, float(threshold), capacity, int(n_sensors), header, index, charge)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# detector-level validation, cluster level: connected components of the digits and their spectra (csrc/pxd_clusters.hip)
+# ---------------------------------------------------------------------------------------------------------
+class PXDClusters:
+    """Device-side result of ``pxd_clusters``: the ``PXDDigits`` it was built from (``digits``), ``label`` int32 ``[capacity]`` (cluster
+    number of digit k) and the cluster table ``first`` / ``size`` / ``charge`` / ``size_u`` / ``size_v`` int32 and ``seed`` uint8, all
+    ``[capacity]`` (a batch has at most as many clusters as digits), ``counts`` int32 ``[N]`` (clusters per image), ``total`` int32
+    ``[1]``.  Only the first ``min(digits.total, capacity)`` labels and the first ``total`` table rows are written."""
+
+    def __init__(self, digits, label, first, size, charge, seed, size_u, size_v, header):
+        self.digits, self.capacity, self.n_sensors, self.shape = digits, digits.capacity, digits.n_sensors, digits.shape
+        self.label, self.first, self.size, self.charge, self.seed, self.size_u, self.size_v = label, first, size, charge, seed, size_u, size_v
+        self.header = header
+        self.counts, self.total = header[:self.shape[0]], header[self.shape[0]:]
+
+    def cpu(self):
+        """One read-back (every array packed into one device tensor, one copy, one wait) -> dict of NumPy arrays trimmed to the true
+        totals: per digit ``index``, ``digit_charge``, ``label``; per cluster ``first``, ``size``, ``charge``, ``seed``, ``size_u``,
+        ``size_v``, ``sensor`` (``first // (H*W) % n_sensors``), ``event``; ``counts [N]``, ``digit_counts [N]``.  Never truncated: when
+        the digit total exceeds the capacity, digits and clusters are run again with ``capacity = total`` (a second read-back, on that
+        path only)."""
+        N, Hh, Ww = self.shape
+        d = self.digits
+        i32 = lambda t: t.to(torch.int32)
+        packed = torch.cat([d.header, self.header, d.index, self.label, self.first, self.size, self.charge, self.size_u, self.size_v,
+                            i32(d.charge), i32(self.seed)]).cpu().numpy()
+        dcounts, dtotal = packed[:N].copy(), int(packed[N])
+        counts, total = packed[N + 1:2 * N + 1].copy(), int(packed[2 * N + 1])
+        if dtotal > self.capacity:
+            full = pxd_clusters(d.images, d.threshold, capacity=dtotal, n_sensors=self.n_sensors)
+            for k in ("digits", "capacity", "label", "first", "size", "charge", "seed", "size_u", "size_v", "header", "counts", "total"):
+                setattr(self, k, getattr(full, k))
+            return full.cpu()
+        C = self.capacity
+        col = lambda k, m: packed[2 * N + 2 + k * C:2 * N + 2 + k * C + m].copy()
+        first = col(2, total)
+        image = first // np.int32(Hh * Ww)
+        return dict(index=col(0, dtotal), label=col(1, dtotal), first=first, size=col(3, total), charge=col(4, total), size_u=col(5, total),
+                    size_v=col(6, total), digit_charge=col(7, dtotal).astype(np.uint8), seed=col(8, total).astype(np.uint8),
+                    sensor=(image % self.n_sensors).astype(np.int32), event=(image // self.n_sensors).astype(np.int32), counts=counts,
+                    digit_counts=dcounts)
+
+
+def pxd_clusters(images_or_digits, threshold=0.0, capacity=None, n_sensors=40):
+    """Clusters of a batch of sensor images ``[N, H, W]`` (fp32 or uint8 device tensor: ``pxd_digits(images, threshold, capacity,
+    n_sensors)`` runs first) or of an existing ``PXDDigits`` (its threshold, capacity and sensors hold): connected components of the
+    digits under 8-connectivity inside an image, numbered by the flat index of their first digit -- the raster numbering of
+    ``scipy.ndimage.label(img > 0, ones((3, 3)))`` per image with a running offset -- with size, summed charge, seed charge and row /
+    column extent per cluster, all integers, bit-identical run to run (csrc/pxd_clusters.hip).
+
+    Launches on the current stream, neither synchronises nor copies; with ``capacity`` given it can be captured into a HIP graph.  When
+    the digit total exceeds the capacity the device result covers the first ``capacity`` digits; ``PXDClusters.cpu()`` reruns instead
+    of handing back a truncated event."""
+    H.require_gpu()
+    d = images_or_digits if isinstance(images_or_digits, PXDDigits) else pxd_digits(images_or_digits, threshold, capacity, n_sensors)
+    N, Hh, Ww = d.shape
+    if Hh * Ww * 255 >= 2 ** 31:
+        raise ValueError(f"pxd_clusters: {Hh} x {Ww} pixels x 255 do not fit the int32 cluster charge")
+    dev, C = d.index.device, d.capacity
+    i32 = lambda: torch.empty(C, dtype=torch.int32, device=dev)
+    label, first, size, charge, size_u, size_v = i32(), i32(), i32(), i32(), i32(), i32()
+    seed = torch.empty(C, dtype=torch.uint8, device=dev)
+    header = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(H.lib().ieagan_pxd_clusters_scratch(N, Hh, Ww, C), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        H.call("ieagan_pxd_clusters", *_ptrs(C, d.index, d.charge), d.total.data_ptr(), N, Hh, Ww, C,
+               *_ptrs(C, label, first, size, charge, seed, size_u, size_v), header.data_ptr(), header.data_ptr() + 4 * N, scratch.data_ptr(),
+               H.stream())
+    return PXDClusters(d, label, first, size, charge, seed, size_u, size_v, header)
+
+
+class PXDClusterStatistics:
+    """Accumulator of per-sensor cluster spectra over batches of sensor images in detector units (``[N, H, W]`` fp32 or uint8, image ``n``
+    is sensor ``n % n_sensors``), beside ``PXDStatistics``: ``update`` runs digits -> clusters -> ``ieagan_pxd_cluster_stats`` on the
+    current stream and neither synchronises nor copies; ``result()`` does the single read-back.  Counters are exact int64.
+    ``capacity`` (digits per update) defaults to that of ``pxd_digits``; an update whose digit total exceeds it is counted on the device
+    and makes ``result()`` raise: a truncated event is never reported."""
+
+    def __init__(self, n_sensors=40, threshold=7.0, capacity=None, device=None):
+        self.n_sensors, self.threshold = int(n_sensors), float(threshold)
+        self.capacity = None if capacity is None else int(capacity)
+        self.device = torch.device(device) if device is not None else None
+        self.reset()
+
+    def reset(self):
+        self.tables = None              # int64 [S * 640 + 1] on the device: the spectra, then the overflow counter
+        self.clusters, self.shape = [], None
+
+    def update(self, images):
+        x = _sensor_images(images, self.n_sensors, "pxd_digits", self.device)       # a wrong dtype or rank is reported as by pxd_digits
+        self.device = self.device or x.device
+        if self.shape not in (None, tuple(x.shape[1:])):
+            raise ValueError(f"PXDClusterStatistics.update: image size {tuple(x.shape[1:])} differs from the accumulated {self.shape}")
+        self.shape = tuple(x.shape[1:])
+        c = pxd_clusters(x, self.threshold, self.capacity, self.n_sensors)
+        N, Hh, Ww = c.shape
+        S = self.n_sensors
+        if self.tables is None:
+            self.tables = torch.zeros(S * H.PXD_CLUSTER_BINS + 1, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            H.call("ieagan_pxd_cluster_stats", *_ptrs(c.capacity, c.first, c.size, c.charge, c.seed, c.size_u, c.size_v), c.total.data_ptr(),
+                   c.digits.total.data_ptr(), N, Hh, Ww, S, c.capacity, self.tables.data_ptr(),
+                   self.tables.data_ptr() + 8 * S * H.PXD_CLUSTER_BINS, H.stream())
+        self.clusters.append(c.counts)
+        return c
+
+    def result(self):
+        """NumPy tables: int64 ``size_spectrum [S, 64]`` (bin ``min(size, 64) - 1``), ``charge_spectrum [S, 256]`` (bin
+        ``min(charge >> 3, 255)``, 8 ADU a bin), ``seed_spectrum [S, 256]``, ``size_u_spectrum`` / ``size_v_spectrum [S, 32]`` (bin
+        ``min(s, 32) - 1``), ``clusters`` int32 ``[events, S]`` (clusters per image) and ``n_events``.  Raises when an update overflowed."""
+        if not self.clusters:
+            raise RuntimeError("PXDClusterStatistics.result() before any update()")
+        S, B = self.n_sensors, H.PXD_CLUSTER_BINS
+        packed = torch.cat([self.tables, torch.cat(self.clusters).to(torch.int64)]).cpu().numpy()      # the one device-to-host copy
+        overflow = int(packed[S * B])
+        if overflow != 0:
+            raise RuntimeError(f"PXDClusterStatistics: {overflow} update(s) held more digits than the capacity"
+                               f"{'' if self.capacity is None else ' of %d' % self.capacity}, their clusters are truncated: "
+                               "pass a larger capacity= to PXDClusterStatistics")
+        rows = packed[:S * B].reshape(S, B)
+        out = {k: rows[:, a:a + n].copy() for k, (a, n) in H.PXD_CLUSTER_COLUMNS.items()}
+        out["clusters"] = packed[S * B + 1:].astype(np.int32).reshape(-1, S)
+        out["n_events"] = int(out["clusters"].shape[0])
+        return out
+
+
+def pxd_cluster_distance(real, fake):
+    """Four distances between two ``PXDClusterStatistics.result()`` tables (float64, host): ``cluster_rate_rel_err`` = mean over the
+    sensors with real clusters of |fake - real| / real of the mean clusters per image; ``size_w1`` (pixels), ``cluster_charge_w1`` (ADU,
+    bins of 8) and ``seed_w1`` (ADU) = 1-D Wasserstein distances between the spectra pooled over the sensors and normalised to 1 (the
+    construction of ``pxd_distance`` for the ADC spectrum), NaN when one side has no cluster at all."""
+    r = np.asarray(real["clusters"], np.float64).mean(0)
+    out = dict(cluster_rate_rel_err=_rel_err(r, np.asarray(fake["clusters"], np.float64).mean(0), r > 0))
+    for name, key, width in (("size_w1", "size_spectrum", 1.0), ("cluster_charge_w1", "charge_spectrum", 8.0), ("seed_w1", "seed_spectrum", 1.0)):
+        out[name] = _w1(real[key], fake[key], width)
+    return out
+
+
+def write_digits(path, event_offsets, sensor, ucell, vcell, charge):
+    """The event file of ``produce.py`` (``.npz``): ``event_offsets`` int64 ``[events + 1]`` (the digits of event ``e`` are
+    ``[event_offsets[e], event_offsets[e + 1])``), ``sensor`` uint8, ``ucell`` uint8, ``vcell`` uint16, ``charge`` uint8."""
+    event_offsets = np.asarray(event_offsets, np.int64)
+    cols = dict(sensor=np.asarray(sensor), ucell=np.asarray(ucell), vcell=np.asarray(vcell), charge=np.asarray(charge))
+    if event_offsets.ndim != 1 or event_offsets.size < 1 or event_offsets[0] != 0 or (np.diff(event_offsets) < 0).any():
+        raise ValueError("write_digits: event_offsets must start at 0 and not decrease")
+    for k, v in cols.items():
+        if v.ndim != 1 or v.size != event_offsets[-1]:
+            raise ValueError(f"write_digits: {k} has {v.size} entries, event_offsets ends at {event_offsets[-1]}")
+    if cols["sensor"].size and (cols["sensor"].max() > 255 or cols["ucell"].max() > 255 or cols["vcell"].max() > 65535):
+        raise ValueError("write_digits: a sensor / ucell / vcell value does not fit the file's uint8 / uint8 / uint16 columns")
+    with open(path, "wb") as fh:
+        np.savez(fh, event_offsets=event_offsets, sensor=cols["sensor"].astype(np.uint8), ucell=cols["ucell"].astype(np.uint8),
+                 vcell=cols["vcell"].astype(np.uint16), charge=cols["charge"].astype(np.uint8))
+
+
+def read_digits(path):
+    """Yields the events of a ``produce.py`` file in the format ``create_g1.generate`` puts on its queue (create_g1.py:79, read by
+    ``DigitCreator.event`` :105-106): ``((sensor, ucell, vcell) lists, charges list)``."""
+    with np.load(path) as t:
+        off, sensor, ucell, vcell, charge = (t[k] for k in ("event_offsets", "sensor", "ucell", "vcell", "charge"))
+    for e in range(off.size - 1):
+        s = slice(int(off[e]), int(off[e + 1]))
+        yield (sensor[s].tolist(), ucell[s].tolist(), vcell[s].tolist()), charge[s].tolist()

@@ -35,9 +35,9 @@ def _all_hit(kind):
     return ev.astype(np.uint8 if kind == "u8" else np.float32)
 
 
-def _pattern(kind, rule):
-    r, c = np.mgrid[0:64, 0:64]
-    ev = np.where(rule(r, c), 8 + (r * 64 + c) % 200, 0)[None]
+def _pattern(kind, rule, side=64):
+    r, c = np.mgrid[0:side, 0:side]
+    ev = np.where(rule(r, c), 8 + (r * side + c) % 200, 0)[None]
     return ev.astype(np.uint8 if kind == "u8" else np.float32)
 
 
@@ -49,6 +49,8 @@ CASES = {
     "every_second_column": lambda kind: _pattern(kind, lambda r, c: c % 2 == 0),
     "all_zero": lambda kind: np.zeros((40, 58, 64), np.uint8 if kind == "u8" else np.float32),
     "40x250x768_structured": lambda kind: CR.cached_structured(40, 250, 768, 22, kind)[0],
+    # capacity 2^20 = 1024 blocks of the cluster launches, the most there are: the scan's one tile is full, its last thread owns real slots
+    "1x1024x1024_isolated": lambda kind: _pattern(kind, lambda r, c: (r % 3 == 1) & (c % 3 == 0), side=1024),
 }
 
 
@@ -112,9 +114,11 @@ def test_kernel_against_checker(case, kind, threshold):
         assert ref["total"] == 32 and (ref["size"] == 64).all() and (ref["size_v"] == 1).all() and (ref["size_u"] == 64).all()
     elif case == "all_zero":
         assert ref["total"] == 0 and ref["label"].size == 0
-    cap = ev.size if ev.size < 10 ** 6 else None
+    elif case == "1x1024x1024_isolated":
+        assert ref["total"] == ref["label"].size == 341 * 342 == 116622 and (ref["size"] == 1).all() and ev.size == 1024 * 1024
+    cap = ev.size if ev.size < 2 * 10 ** 6 else None
     c = utils.pxd_clusters(torch.from_numpy(ev).to(DEV), threshold=threshold, capacity=cap, n_sensors=n)
-    assert c.label.is_cuda and c.capacity == (ev.size if ev.size < 10 ** 6 else max(1024, ev.size // 16)) == c.digits.capacity
+    assert c.label.is_cuda and c.capacity == (ev.size if ev.size < 2 * 10 ** 6 else max(1024, ev.size // 16)) == c.digits.capacity
     _check(c, ref, f"{case} {kind} cut {threshold}")
     host = c.cpu()
     for k in ("index", "digit_charge", "label", "counts") + TABLE:
