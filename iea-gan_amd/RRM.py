@@ -48,8 +48,8 @@ class MultiheadAttention(nn.Module):
             import _hip
             _hip.require_gpu()
             raise RuntimeError("RRM of the MI355X path takes HIP tensors (no CPU fallback)")
-        if S <= 64:
-            import ops                                                    # fused HIP core: S x S affinity in LDS
+        import ops
+        if ops.rrm_attention_fits(S, self.head_dim):                      # fused HIP core: S x S affinity in LDS
             vals, att = ops.RRMAttentionFn.apply(qkv, self.num_heads)
         else:                                                             # > 64 tokens (joint fake+real pass): library path
             q, k, v = qkv.reshape(B, S, self.num_heads, 3 * self.head_dim).permute(0, 2, 1, 3).chunk(3, dim=-1)
@@ -73,12 +73,16 @@ class EncoderBlock(nn.Module):
         self.dropout = nn.Dropout(dropout)
 
     def _fusable(self, x):
-        """The stage-wise fused HIP block (ops.RRMBlockFn) takes <= 64 tokens per event (attention affinity in LDS) and channel
-        counts that are multiples of 16; anything else (e.g. the 80 / 120 tokens of a joint fake + real pass) runs op by op."""
+        """The stage-wise fused HIP block (ops.RRMBlockFn) takes the token counts of ops.rrm_attention_fits (<= 64 per event, attention
+        affinity and its backward in LDS) and channel counts that are multiples of 16; anything else (e.g. the 80 / 120 tokens of a joint
+        fake + real pass) runs op by op."""
         at = self.self_attn
         dims = (at.qkv_proj.in_features, at.qkv_proj.out_features, self.linear_net[0].out_features)
-        return x.is_cuda and x.dim() == 3 and x.shape[1] <= 64 and all(d % 16 == 0 for d in dims) and dims[1] == 3 * dims[0] \
-            and at.o_proj.in_features == at.o_proj.out_features == dims[0] and self.linear_net[3].out_features == dims[0]
+        if not x.is_cuda:
+            return False
+        import ops
+        return x.dim() == 3 and ops.rrm_attention_fits(x.shape[1], at.head_dim) and all(d % 16 == 0 for d in dims) \
+            and dims[1] == 3 * dims[0] and at.o_proj.in_features == at.o_proj.out_features == dims[0] and self.linear_net[3].out_features == dims[0]
 
     def forward(self, x, recs=None, prefix=""):
         if FUSED and self._fusable(x):

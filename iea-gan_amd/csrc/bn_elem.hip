@@ -741,6 +741,8 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const bf16* __restric
 }
 
 extern "C" int ieagan_nchw_to_nhwc(const float* in, void* out, float* stats, int N, int C, int HW, int n_per_event, void* stream) {
+    CHECK_ARG(in != nullptr && out != nullptr, "nchw_to_nhwc: null pointer");
+    CHECK_ARG(N >= 1 && C >= 1 && HW >= 1, "nchw_to_nhwc: N=%d C=%d HW=%d", N, C, HW);
     CHECK_ARG(n_per_event >= 0 && (n_per_event == 0 || N % n_per_event == 0), "nchw_to_nhwc: N=%d is not a whole number of events of %d images", N, n_per_event);
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("nchw_to_nhwc", 0.0, 6.0 * N * C * (double)HW, st);
@@ -750,6 +752,8 @@ extern "C" int ieagan_nchw_to_nhwc(const float* in, void* out, float* stats, int
 }
 
 extern "C" int ieagan_nhwc_to_nchw(const void* in, float* out, int N, int C, int HW, void* stream) {
+    CHECK_ARG(in != nullptr && out != nullptr, "nhwc_to_nchw: null pointer");
+    CHECK_ARG(N >= 1 && C >= 1 && HW >= 1, "nhwc_to_nchw: N=%d C=%d HW=%d", N, C, HW);
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("nhwc_to_nchw", 0.0, 6.0 * N * C * (double)HW, st);
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(cdiv(HW, 32), cdiv(C, 32), N), dim3(256), 0, st, (const bf16*)in, out, C, HW);

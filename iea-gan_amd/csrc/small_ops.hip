@@ -361,11 +361,26 @@ __global__ __launch_bounds__(256) void rrm_attn_bwd4_kernel(const float* __restr
     }
 }
 
+// Dynamic LDS of the two launches: q, k, v (and dout) rows of hd + pad floats, the S x S affinity (and its gradient).
+static size_t rrm_attention_lds(int S, int hd, bool bwd) {
+    const size_t ld = hd + ((hd & 3) == 0 ? 4 : 1);
+    return ((bwd ? 4 : 3) * S * ld + (bwd ? 2 : 1) * (size_t)S * S) * 4;
+}
+
+// One shape check for both entries, on the LARGER (backward) footprint: a forward that ran always has a backward that can run.
+static int rrm_attention_check(const void* a, const void* b, const void* c, const void* d, int B, int S, int H, int hd) {
+    CHECK_ARG(a != nullptr && b != nullptr && c != nullptr && d != nullptr, "rrm_attention: null pointer");
+    CHECK_ARG(B >= 1 && H >= 1 && hd >= 1, "rrm_attention: B=%d H=%d hd=%d", B, H, hd);
+    CHECK_ARG(S >= 1 && S <= SMAX, "rrm_attention: S must be <= %d", SMAX);
+    CHECK_ARG(rrm_attention_lds(S, hd, true) <= 150 * 1024, "rrm_attention: head does not fit LDS (S=%d hd=%d: the backward needs %zu bytes of %d)",
+              S, hd, rrm_attention_lds(S, hd, true), 150 * 1024);
+    return 0;
+}
+
 extern "C" int ieagan_rrm_attention_fwd(const float* qkv, float* out, float* att, int B, int S, int H, int hd, void* stream) {
-    CHECK_ARG(S >= 1 && S <= SMAX && hd >= 1, "rrm_attention: S must be <= %d", SMAX);
+    if (const int rc = rrm_attention_check(qkv, out, att, qkv, B, S, H, hd)) return rc;
     const bool v4 = (hd & 3) == 0;
-    const size_t lds = (size_t)(3 * S * (hd + (v4 ? 4 : 1)) + S * S) * 4;
-    CHECK_ARG(lds <= 150 * 1024, "rrm_attention: head does not fit LDS");
+    const size_t lds = rrm_attention_lds(S, hd, false);
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("rrm_attention_fwd", 4.0 * B * H * S * S * hd, 0.0, st);
     if (v4) hipLaunchKernelGGL(rrm_attn_fwd4_kernel, dim3(H, B), dim3(256), lds, st, qkv, out, att, S, H, hd);
@@ -376,10 +391,9 @@ extern "C" int ieagan_rrm_attention_fwd(const float* qkv, float* out, float* att
 
 extern "C" int ieagan_rrm_attention_bwd(const float* qkv, const float* att, const float* dout, float* dqkv, int B, int S, int H, int hd,
                                         void* stream) {
-    CHECK_ARG(S >= 1 && S <= SMAX && hd >= 1, "rrm_attention: S must be <= %d", SMAX);
+    if (const int rc = rrm_attention_check(qkv, att, dout, dqkv, B, S, H, hd)) return rc;
     const bool v4 = (hd & 3) == 0;
-    const size_t lds = (size_t)(4 * S * (hd + (v4 ? 4 : 1)) + 2 * S * S) * 4;
-    CHECK_ARG(lds <= 150 * 1024, "rrm_attention: head does not fit LDS");
+    const size_t lds = rrm_attention_lds(S, hd, true);
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("rrm_attention_bwd", 8.0 * B * H * S * S * hd, 0.0, st);
     if (v4) hipLaunchKernelGGL(rrm_attn_bwd4_kernel, dim3(H, B), dim3(256), lds, st, qkv, att, dout, dqkv, S, H, hd);
@@ -713,6 +727,8 @@ __global__ __launch_bounds__(256) void relu_sum_pool_bwd_kernel(const bf16* __re
 }
 
 extern "C" int ieagan_relu_sum_pool(const void* x, float* out, int N, int HW, int C, void* stream) {
+    CHECK_ARG(x != nullptr && out != nullptr, "relu_sum_pool: null pointer");
+    CHECK_ARG(N >= 1 && HW >= 1 && C >= 1, "relu_sum_pool: N=%d HW=%d C=%d", N, HW, C);
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof("relu_sum_pool", 0.0, 2.0 * N * HW * (double)C, st);
     hipLaunchKernelGGL(relu_sum_pool_kernel, dim3(cdiv(C, 256), N), dim3(256), 0, st, (const bf16*)x, out, HW, C);
@@ -721,6 +737,8 @@ extern "C" int ieagan_relu_sum_pool(const void* x, float* out, int N, int HW, in
 }
 
 extern "C" int ieagan_relu_sum_pool_bwd(const void* x, const float* dh, void* dx, int N, int HW, int C, void* stream) {
+    CHECK_ARG(x != nullptr && dh != nullptr && dx != nullptr, "relu_sum_pool_bwd: null pointer");
+    CHECK_ARG(N >= 1 && HW >= 1 && C >= 1, "relu_sum_pool_bwd: N=%d HW=%d C=%d", N, HW, C);
     hipStream_t st = (hipStream_t)stream;
     const long total = (long)N * HW * C;
     ProfScope prof("relu_sum_pool_bwd", 0.0, 4.0 * total, st);

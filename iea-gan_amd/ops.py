@@ -1406,9 +1406,17 @@ class NLAttentionFn(torch.autograd.Function):
 # =====================================================================================================
 # small fused kernels: RRM attention core, loss block, D-head pooling
 # =====================================================================================================
+def rrm_attention_fits(S: int, hd: int) -> bool:
+    """The shapes ``ieagan_rrm_attention_fwd`` / ``_bwd`` take (csrc/small_ops.hip: rrm_attention_check): S <= 64 tokens and the backward's
+    LDS -- q, k, v, dout rows of hd + 4 floats (hd + 1 when hd % 4 != 0) and two S x S matrices -- within 150 KB.  hd = 64: S <= 64;
+    hd = 128: S <= 59."""
+    ld = hd + (4 if hd % 4 == 0 else 1)
+    return 1 <= S <= 64 and (4 * S * ld + 2 * S * S) * 4 <= 150 * 1024
+
+
 class RRMAttentionFn(torch.autograd.Function):
     """softmax(q k^T / sqrt(hd)) v per (batch, head) on the packed projection [B,S,H*3*hd] -> [B,S,H*hd];
-    the S x S affinity lives in LDS (RRM.py:10-16, 46-58)."""
+    the S x S affinity lives in LDS (RRM.py:10-16, 46-58).  Shapes: ``rrm_attention_fits``."""
 
     @staticmethod
     def forward(ctx, qkv, num_heads):
@@ -1558,7 +1566,8 @@ class EmbedNormFn(torch.autograd.Function):
 
 
 class RRMBlockFn(torch.autograd.Function):
-    """One pre-LN encoder block of the Relational Reasoning Module (reference RRM.py:66-109) on [B, S <= 64, E] tokens, stage-wise
+    """One pre-LN encoder block of the Relational Reasoning Module (reference RRM.py:66-109) on [B, S, E] tokens with
+    ``rrm_attention_fits(S, E // heads)`` (S <= 64 at a head width of 64, S <= 59 at 128: the attention BACKWARD's LDS), stage-wise
     fused: [LN1 + qkv] -> [attention core] -> [o proj + residual] -> [LN2 + FFN1 + ReLU] -> [FFN2 + residual]: five launches
     forward, seven backward (+ one per spectrally normalised weight).  ``params`` = (norm1.w, norm1.b, qkv.w, qkv.b, o.w, o.b,
     norm2.w, norm2.b, ffn1.w, ffn1.b, ffn2.w, ffn2.b); ``recs``: the four SNRecords of the linear layers (SNLinear flavour, D) or

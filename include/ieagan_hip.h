@@ -328,7 +328,9 @@ int ieagan_nl_attention_bwd(const void* Q, const void* K, const void* V, const v
 
 /* ---- small single-workgroup kernels (small_ops.hip) --------------------------------------------------
  * RRM attention core: softmax(q k^T / sqrt(hd)) v per (batch, head), S <= 64 tokens, affinity in LDS
- * (RRM.py:10-16, 46-58).  qkv [B,S,H,3*hd] (packed projection), out [B,S,H*hd], att [B,H,S,S], all fp32. */
+ * (RRM.py:10-16, 46-58).  qkv [B,S,H,3*hd] (packed projection), out [B,S,H*hd], att [B,H,S,S], all fp32.
+ * Both entries take the same shapes: S <= 64 and the BACKWARD's LDS, (4 S (hd + 4) + 2 S^2) * 4 bytes (hd + 1 when hd % 4 != 0),
+ * within 150 KB -- hd = 64: S <= 64, hd = 128: S <= 59.  Any other shape is refused by both with the same message. */
 int ieagan_rrm_attention_fwd(const float* qkv, float* out, float* att, int B, int S, int H, int hd, void* stream);
 int ieagan_rrm_attention_bwd(const float* qkv, const float* att, const float* dout, float* dqkv, int B, int S, int H, int hd,
                              void* stream);
