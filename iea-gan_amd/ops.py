@@ -13,6 +13,7 @@ dsumsq), so one BN layer costs one extra read in forward and no standalone pass 
 from __future__ import annotations
 
 import math
+import types
 from typing import Optional
 
 import torch
@@ -108,20 +109,13 @@ class ExecOptions:
     wgrad_side_stream   weight-gradient launches of a training backward pass on a side stream (nothing in the pass reads dW before the
                         batched spectral-norm backward at its end, ``SNPass.flush`` joins)
     two_stage_wgrad     conv_wgrad: partial slabs + reduction launch instead of float atomics when the atomic volume is large
-    use_tr_read         ds_read_b64_tr_b16 operand reads in conv_wgrad (False: scalar LDS reads, the test reference)
     fuse_bn_backward    BatchNorm-apply backward inside the dgrad epilogue (False: the stand-alone prologue_bwd pass)
     fuse_shortcut_grad  residual-shortcut gradients added inside the dx-producing kernel (False: autograd adds)
     fuse_1x1_backward / fuse_3x3_backward (+ *_min_pixels)   the whole-backward kernels conv1x1_bwd / conv3x3_bwd (False: separate launches)
-    fuse_d_stem         D.input_conv + the first DBlock's conv1 / conv_sc / pooled shortcut in one launch each way
-    b1_flags            ieagan_conv1x1_bwd_desc.flags (benchmarks: H.B1_OCC2 / H.B1_OCC3)
-    fused_reduce_side_stream   the slab folds of the whole-backward kernels on the weight-gradient side stream (with wgrad_side_stream).
-                        OFF: measured 36.75-37.0 vs 34.75-34.97 ms per step on one box -- the side stream then sits behind every fused kernel
-                        of the large maps and the weight gradients queued after it start late
-    fused_reduce_batched       the slab folds of the whole-backward kernels of a pass in ONE launch at the end of the pass (``SNPass.flush``:
-                        nothing reads dW earlier) instead of one launch behind each of them"""
-    FIELDS = dict(wgrad_side_stream=True, two_stage_wgrad=True, use_tr_read=True, fuse_bn_backward=True, fuse_shortcut_grad=True,
+    fuse_d_stem         D.input_conv + the first DBlock's conv1 / conv_sc / pooled shortcut in one launch each way"""
+    FIELDS = dict(wgrad_side_stream=True, two_stage_wgrad=True, fuse_bn_backward=True, fuse_shortcut_grad=True,
                   fuse_1x1_backward=True, fuse_1x1_min_pixels=1 << 16, fuse_3x3_backward=True, fuse_3x3_min_pixels=1 << 16,
-                  fuse_d_stem=True, b1_flags=0, fused_reduce_side_stream=False, fused_reduce_batched=True)
+                  fuse_d_stem=True)
     __slots__ = tuple(FIELDS)
 
     def __init__(self, like=None, **kw):
@@ -217,7 +211,10 @@ class SNPass:
         if self.side is not None:
             cur.wait_stream(self.side)
             self.side = None
-        if self.reduces:                # the slab sets the whole-backward kernels of this pass left behind (fused_reduce_batched)
+        if self.reduces:                # the slab sets the whole-backward kernels of this pass left behind
+            if len({dwp.data_ptr() for _, dwp, *_ in self.reduces}) != len(self.reduces):
+                # the batched fold adds a single slab into dW without atomics: two sets on one dW would lose a contribution
+                raise RuntimeError("two slab sets of one backward pass target the same weight gradient (a layer applied twice in one pass?)")
             items = (H.ReduceItem * len(self.reduces))(*[H.ReduceItem(ws.data_ptr(), dwp.data_ptr(), S, Cout, kpad, K)
                                                         for ws, dwp, S, Cout, kpad, K in self.reduces])
             H.call("ieagan_wgrad_reduce_batched", items, len(self.reduces), H.stream())
@@ -516,6 +513,8 @@ class BNFinalizeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, stats, gb, bank, col_gain, col_bias, C, run_mean, run_var, count, eps, momentum, training, events=1, link=None):
         """``count``: elements per channel of ONE event; ``stats`` [E, STAT_REPL, 2, C]."""
+        if not (stats is None or stats.dim() == 4):
+            raise ValueError(f"BNFinalizeFn: statistics must be [E, slots, 2, C], got {tuple(stats.shape)}")
         ctx.link = link
         N, ld = gb.shape
         dev = gb.device
@@ -566,6 +565,8 @@ class BNFinalizePlainFn(torch.autograd.Function):
     def forward(ctx, stats, gain, bias, run_mean, run_var, count, eps, momentum, training, events=1, n_images=1):
         """One event: per-channel scale / shift [C].  E > 1 events: one row per image, [N, C] (every image takes the
         statistics of its own event)."""
+        if not (stats is None or stats.dim() == 4):
+            raise ValueError(f"BNFinalizePlainFn: statistics must be [E, slots, 2, C], got {tuple(stats.shape)}")
         C = gain.numel()
         dev = gain.device
         rows = 1 if events == 1 else n_images
@@ -713,57 +714,129 @@ def _placeholder(like):
     return _PLACEHOLDERS[key]
 
 
-# The whole backward of a 1x1 convolution on a large map in ONE launch (csrc/conv1x1_bwd.hip): effgrad + dgrad + prologue backward +
-# wgrad + bias column sums, every operand tile read once (ExecOptions.fuse_1x1_backward; tests compare it with the separate launches).
+# =====================================================================================================
+# Shared steps of the conv backward paths (the generic launch sequence and the two whole-backward kernels)
+# =====================================================================================================
+def _unpack(ctx):
+    """Everything one ``ConvFn`` node saved for its backward, as one object."""
+    b = types.SimpleNamespace(rec=ctx.rec, events=ctx.events, flags=ctx.flags, need=ctx.needs_input_grad, ra_shape=ctx.ra_shape,
+                              bias_ref=ctx.bias_ref)
+    b.x, b.weight, b.scale, b.shift, b.out = ctx.saved_tensors
+    b.opts = opts_of(b.rec)
+    b.taps, b.rs, b.relu, b.Ca, b.ra_rs, b.nstride, b.Hc, b.Wc = ctx.cfg
+    b.has_bias, b.has_aff, b.has_ra, b.has_rb = ctx.has
+    b.res_out, b.res_in = ctx.links
+    b.N, b.Hs, b.Ws, b.Cx = b.x.shape
+    b.Cin, b.Cout, b.dev = b.rec.cin, b.rec.out, b.x.device
+    return b
 
 
-def _fused_bwd_launch(name, d, rec, ws, dwp, Cout, K, operands):
-    """Launch a whole-backward kernel whose partial dW slabs sit in ``ws``.  ``ExecOptions.fused_reduce_side_stream`` (off by default: it
-    measured 2 ms slower) sends the slab fold (``wgrad_reduce``, ~10 us + a launch boundary per layer) to the weight-gradient side stream:
-    nothing reads dW before the end of the pass (``SNPass.flush`` joins the side stream)."""
-    o = opts_of(rec)
-    side_ok = ws is not None and o.wgrad_side_stream and o.fused_reduce_side_stream and getattr(rec, "deferred", False)
+def _row_stride(dout, Cout, Hc, Wc):
+    """Row stride the kernels can read the out-gradient with: ``Cout`` for a packed tensor, ``stride[2]`` for a channel slice of a wider
+    NHWC tensor (concat shortcut of a D block), None when it needs a packed copy."""
+    if dout.is_contiguous():
+        return Cout
+    st = dout.stride()
+    ok = (st[3] == 1 and st[2] % 8 == 0 and st[2] >= Cout and st[1] == Wc * st[2] and st[0] == Hc * Wc * st[2]
+          and dout.data_ptr() % 16 == 0)
+    return st[2] if ok else None
+
+
+def _bn_param_grads(scale, acc, nstride):
+    """(dscale, dshift) from the replicated per-image accumulators ``acc`` [N, slots, 2, C] of a BatchNorm-apply backward: handed to the
+    finalize backward through the ``BNLink`` of ``scale`` (autograd gets placeholders), else folded here."""
+    link = getattr(scale, "_bn_link", None)
+    if link is not None:
+        link.acc = acc
+        return (_placeholder(scale),) * 2
+    sums = acc.sum(1)                   # stand-alone use (tests)
+    dshift, dscale = sums[:, 0], sums[:, 1]
+    if nstride == 0:
+        dshift, dscale = dshift.sum(0), dscale.sum(0)
+    return dscale, dshift
+
+
+def _residual_grads(b, gl):
+    """(d_ra, d_rb): gradients of the residual operands from the (effective) out-gradient ``gl``, packed or a channel slice."""
+    d_ra = d_rb = None
+    if b.has_ra and b.need[5]:
+        rshape = b.ra_shape
+        if b.res_out is not None:           # consumed in-kernel by the block's first conv
+            b.res_out.deposit(gl, gl.stride()[2] if not gl.is_contiguous() else b.Cout, b.Ca, b.ra_rs)
+        elif b.ra_rs == 0:
+            if b.Ca == b.Cout and rshape[-1] == b.Cout:
+                d_ra = gl
+            else:
+                d_ra = torch.zeros(rshape, dtype=BF16, device=b.dev)
+                d_ra[..., :b.Ca] = gl[..., :b.Ca]
+        else:
+            d_ra = torch.empty(rshape, dtype=BF16, device=b.dev)
+            H.call("ieagan_res_bwd", gl.contiguous().data_ptr(), b.Cout, d_ra.data_ptr(), rshape[-1], b.Ca, b.ra_rs, b.N, rshape[1], rshape[2],
+                   H.stream())
+    if b.has_rb and b.need[6]:
+        d_rb = gl[..., b.Ca:]
+    return d_ra, d_rb
+
+
+def _fused_buffers(d, kernel, N, Cin, has_aff, dev):
+    """Size and attach what a whole-backward launch ``d`` of ``kernel`` ('conv1x1_bwd' / 'conv3x3_bwd') needs besides its operands: the
+    per-image BatchNorm accumulators (one slot per block of the image: single adder, bit-reproducible) and the dW slab workspace.
+    Returns (acc, ws), None where the launch takes none."""
+    acc = ws = None
+    if has_aff:
+        d.bn_slots = getattr(H.lib(), f"ieagan_{kernel}_slots")(d)
+        if d.bn_slots <= 0:
+            raise RuntimeError(f"ieagan_{kernel}_slots failed: {H.lib().ieagan_last_error().decode()}")
+        acc = zeros((N, d.bn_slots, 2, Cin), dev)
+        d.bn_acc = acc.data_ptr()
+    ws_n = getattr(H.lib(), f"ieagan_{kernel}_workspace")(d)
+    if ws_n < 0:
+        raise RuntimeError(f"ieagan_{kernel}_workspace failed: {H.lib().ieagan_last_error().decode()}")
+    if ws_n > 0:
+        ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
+        d.partials = ws.data_ptr()
+    return acc, ws
+
+
+def _dgrad(b, g, Cg, out, *, link=None, link_rs=0, link_scale=1.0, mask=None, stats=None, bnb=None, flags=0, npe=0):
+    """conv_forward driven as the data gradient of layer ``b`` (rec, N, Hc, Wc, Cin, Cout, taps): channels swapped, the transposed pack
+    ``rec.w_bwd``, no prologue, no bias.  ``link`` = (lg, lC, lCa): a shortcut gradient added in the epilogue (resampled by ``link_rs``,
+    times ``link_scale``); ``mask`` / ``stats`` / ``bnb`` / ``flags`` / ``npe`` as in ``_conv_launch``, whose result is returned."""
+    lg, lC, lCa = link if link is not None else (None, 0, 0)
+    return _conv_launch(g, Cg, b.Hc, b.Wc, 0, None, None, 0, False, b.N, b.Hc, b.Wc, b.Cout, b.Cin, b.taps, b.rec.kpad2, b.rec.w_bwd, None,
+                        lg, lC, lCa, link_rs, None, 0, mask, out, stats, ra_scale=link_scale, npe=npe, flags=flags, bnb=bnb)
+
+
+def _conv_grads(dx=None, dW=None, dbias=None, dscale=None, dshift=None, d_ra=None, d_rb=None):
+    """The gradients of ``ConvFn.forward``'s 18 inputs."""
+    return (dx, dW, dbias, dscale, dshift, d_ra, d_rb) + (None,) * 11
+
+
+def _fused_bwd_launch(name, d, rec, ws, dwp, Cout, K):
+    """Launch a whole-backward kernel whose partial dW slabs sit in ``ws``.  In a training pass with a scratch arena the slabs are left to
+    ``SNPass.flush``, which folds the slab sets of the whole pass in one launch (nothing reads dW earlier); else the kernel folds them."""
     pass_ = getattr(rec, "pass_", None)
-    batch_ok = (not side_ok and ws is not None and o.fused_reduce_batched and getattr(rec, "deferred", False) and pass_ is not None
-                and pass_.arena is not None)
-    if side_ok or batch_ok:
+    batched = ws is not None and getattr(rec, "deferred", False) and pass_ is not None and pass_.arena is not None
+    if batched:
         d.flags |= H.BWD_NO_REDUCE
     H.call(name, d, H.stream())
-    if batch_ok:                        # folded with the other slab sets of the pass in SNPass.flush
+    if batched:
         pass_.reduces.append((ws, dwp, ws.numel() // (Cout * rec.kpad), Cout, rec.kpad, K))
-        return
-    if side_ok:
-        dev = ws.device
-        fork = torch.cuda.Event()
-        fork.record(torch.cuda.current_stream())
-        side = wgrad_stream(dev)
-        with torch.cuda.stream(side):
-            side.wait_event(fork)
-            H.call("ieagan_wgrad_reduce", ws.data_ptr(), dwp.data_ptr(), ws.numel() // (Cout * rec.kpad), Cout, rec.kpad, K, H.stream())
-        for t in (ws,) + tuple(operands):           # read by the side stream after this node has handed them back to the pool
-            if t is not None:
-                t.record_stream(side)
-        rec.pass_.side = side
 
 
-def _fused_1x1_eligible(ctx, dout, dstats):
+# The whole backward of a 1x1 convolution on a large map in ONE launch (csrc/conv1x1_bwd.hip): effgrad + dgrad + prologue backward +
+# wgrad + bias column sums, every operand tile read once (ExecOptions.fuse_1x1_backward; tests compare it with the separate launches).
+def _fused_1x1_eligible(b, dout, dstats):
     """Can ``ConvFn.backward`` take the fused 1x1 backward for this node?  (shape instantiated, big map, both gradients wanted, a
     shortcut-gradient link the kernel can add in place.)"""
-    rec = ctx.rec
-    o = opts_of(rec)
+    rec, o, rs, relu, has_aff, res_out, res_in, need = b.rec, b.opts, b.rs, b.relu, b.has_aff, b.res_out, b.res_in, b.need
     if not o.fuse_1x1_backward:
         return False
-    taps, rs, relu, Ca, ra_rs, nstride, Hc, Wc = ctx.cfg
-    need = ctx.needs_input_grad
-    has_bias, has_aff, has_ra, has_rb = ctx.has
-    res_out, res_in = ctx.links
-    x = ctx.saved_tensors[0]
-    N = x.shape[0]
-    if taps != 1 or rs not in (0, 2) or not need[0] or not need[1] or Wc % 32 != 0 or N * Hc * Wc < o.fuse_1x1_min_pixels:
+    if b.taps != 1 or rs not in (0, 2) or not need[0] or not need[1] or b.Wc % 32 != 0 or b.N * b.Hc * b.Wc < o.fuse_1x1_min_pixels:
         return False
     if not H.lib().ieagan_conv1x1_bwd_supported(rec.cin, rec.out, rs, int(has_aff)):
         return False
-    if isinstance(res_in, SumLink) or (has_aff and (rs != 0 or ctx.events > 1 and nstride == 0)):
+    if isinstance(res_in, SumLink) or (has_aff and (rs != 0 or b.events > 1 and b.nstride == 0)):
         return False
     if res_in is not None and res_in.ready:
         if rs == 2 and not (res_out is None and not relu and not has_aff):
@@ -774,162 +847,210 @@ def _fused_1x1_eligible(ctx, dout, dstats):
         return False                # conv_sc whose link was not produced: leave the bookkeeping to the generic path
     if rs == 2 and rec.cin != 16 and (relu or res_in is None or not res_in.ready):
         return False                # dx at source resolution of a pooled source exists for Cin = 16 only
-    st = dout.stride()
-    ok_stride = dout.is_contiguous() or (st[3] == 1 and st[2] % 8 == 0 and st[2] >= rec.out and st[1] == Wc * st[2] and
-                                         st[0] == Hc * Wc * st[2] and dout.data_ptr() % 16 == 0)
-    return ok_stride
+    return _row_stride(dout, rec.out, b.Hc, b.Wc) is not None
 
 
-def _conv1x1_backward_fused(ctx, dout, dstats):
-    x, weight, scale, shift, out = ctx.saved_tensors
-    rec = ctx.rec
-    taps, rs, relu, Ca, ra_rs, nstride, Hc, Wc = ctx.cfg
-    has_bias, has_aff, has_ra, has_rb = ctx.has
-    res_out, res_in = ctx.links
-    N, Hs, Ws, Cx = x.shape
-    Cout, Cin = rec.out, rec.cin
-    dev = x.device
-    need = ctx.needs_input_grad
-    g = dout
-    Cg = Cout if dout.is_contiguous() else dout.stride()[2]
+def _conv1x1_backward_fused(b, dout, dstats):
+    x, rec, need, res_in = b.x, b.rec, b.need, b.res_in
+    N, Hc, Wc, Cin, Cout, dev = b.N, b.Hc, b.Wc, b.Cin, b.Cout, b.dev
+    Cg = _row_stride(dout, Cout, Hc, Wc)
     eff = dstats is not None
     # g_eff has other consumers than this layer's own gradients when the shortcut operands need it: the kernel then stores it
-    shortcut_needs_g = (has_ra and need[5]) or (has_rb and need[6])
+    shortcut_needs_g = (b.has_ra and need[5]) or (b.has_rb and need[6])
     geff = torch.empty(N, Hc, Wc, Cout, dtype=BF16, device=dev) if (eff and shortcut_needs_g) else None
     dstat = dstats[:, 0].contiguous() if eff else None
-    colsum = sn_scratch(rec, "b", (STAT_REPL, Cout), dev) if (has_bias and need[2]) else None
+    colsum = sn_scratch(rec, "b", (STAT_REPL, Cout), dev) if (b.has_bias and need[2]) else None
     dwp = sn_scratch(rec, "w", (Cout, rec.kpad), dev)
     # ---- shortcut-gradient link into dx
     lg = lC = lCa = lmode = None
     if res_in is not None and res_in.ready:
         lg, lC, lCa, lmode = res_in.take()
-    conv_sc = rs == 2 and lg is not None            # D block conv_sc: plain da at the pooled resolution + the identity part, re-deposited
+    conv_sc = b.rs == 2 and lg is not None          # D block conv_sc: plain da at the pooled resolution + the identity part, re-deposited
     out_mode = 1 if conv_sc else 0
     if conv_sc:
         lmode = 0                                   # the deposited gradient lives at the block OUTPUT (= pooled) resolution
-    dx = torch.empty((N, Hc, Wc, Cin) if out_mode == 1 else (N, Hs, Ws, Cin), dtype=BF16, device=dev)
-    d = H.Conv1x1BwdDesc(N, Hc, Wc, Cin, Cout, rec.kpad, rec.kpad2, H.src_desc(x, Cx, Hs, Ws, rs, scale, shift, nstride, relu),
-                         g.data_ptr(), Cg, H.ptr(out) if eff else None, H.ptr(dstat), N // ctx.events, H.ptr(geff), rec.w_bwd.data_ptr(),
-                         H.ptr(lg), lC or 0, lCa or 0, lmode or 0, dx.data_ptr(), out_mode, 16 if has_aff else None, dwp.data_ptr(), None, H.ptr(colsum),
-                         opts_of(rec).b1_flags, 0)
-    acc = None
-    if has_aff:         # per-image BatchNorm accumulators: one slot per block of the image (single adder: bit-reproducible)
-        d.bn_slots = H.lib().ieagan_conv1x1_bwd_slots(d)
-        if d.bn_slots <= 0:
-            raise RuntimeError(f"ieagan_conv1x1_bwd_slots failed: {H.lib().ieagan_last_error().decode()}")
-        acc = zeros((N, d.bn_slots, 2, Cin), dev)
-        d.bn_acc = acc.data_ptr()
-    ws_n = H.lib().ieagan_conv1x1_bwd_workspace(d)
-    ws = None
-    if ws_n > 0:
-        ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
-        d.partials = ws.data_ptr()
-    _fused_bwd_launch("ieagan_conv1x1_bwd", d, rec, ws, dwp, Cout, Cin, ())
-    # ---- residual operands (as the generic path, on g_eff)
-    gl = geff if eff else g
-    d_ra = d_rb = None
-    if has_ra and need[5]:
-        rshape = ctx.ra_shape
-        if res_out is not None:
-            res_out.deposit(gl, gl.stride()[2] if not gl.is_contiguous() else Cout, Ca, ra_rs)
-        elif ra_rs == 0:
-            if Ca == Cout and rshape[-1] == Cout:
-                d_ra = gl
-            else:
-                d_ra = torch.zeros(rshape, dtype=BF16, device=dev)
-                d_ra[..., :Ca] = gl[..., :Ca]
-        else:
-            d_ra = torch.empty(rshape, dtype=BF16, device=dev)
-            H.call("ieagan_res_bwd", gl.contiguous().data_ptr(), Cout, d_ra.data_ptr(), rshape[-1], Ca, ra_rs, N, rshape[1], rshape[2],
-                   H.stream())
-    if has_rb and need[6]:
-        d_rb = gl[..., Ca:]
-    dscale = dshift = None
-    if has_aff:
-        bn_link = getattr(scale, "_bn_link", None)
-        if bn_link is not None:
-            bn_link.acc = acc
-            dscale = dshift = _placeholder(scale)
-        else:                       # stand-alone use (tests): fold the replicated per-image accumulators here
-            sums = acc.sum(1)
-            dshift, dscale = sums[:, 0], sums[:, 1]
-            if nstride == 0:
-                dshift, dscale = dshift.sum(0), dscale.sum(0)
+    dx = torch.empty((N, Hc, Wc, Cin) if out_mode == 1 else (N, b.Hs, b.Ws, Cin), dtype=BF16, device=dev)
+    d = H.Conv1x1BwdDesc(N, Hc, Wc, Cin, Cout, rec.kpad, rec.kpad2, H.src_desc(x, b.Cx, b.Hs, b.Ws, b.rs, b.scale, b.shift, b.nstride, b.relu),
+                         dout.data_ptr(), Cg, H.ptr(b.out) if eff else None, H.ptr(dstat), N // b.events, H.ptr(geff), rec.w_bwd.data_ptr(),
+                         H.ptr(lg), lC or 0, lCa or 0, lmode or 0, dx.data_ptr(), out_mode, 16 if b.has_aff else None, dwp.data_ptr(), None,
+                         H.ptr(colsum), 0, 0)
+    acc, ws = _fused_buffers(d, "conv1x1_bwd", N, Cin, b.has_aff, dev)
+    _fused_bwd_launch("ieagan_conv1x1_bwd", d, rec, ws, dwp, Cout, Cin)
+    d_ra, d_rb = _residual_grads(b, geff if eff else dout)         # as the generic path, on g_eff
+    dscale, dshift = _bn_param_grads(b.scale, acc, b.nstride) if b.has_aff else (None, None)
     if conv_sc:
         res_in.deposit(dx, Cin, Cin, 2)
         dx = None
-    dW, dbias = sn_backward(dwp, weight, rec, colsum, ctx.bias_ref)
-    return dx, dW, dbias, dscale, dshift, d_ra, d_rb, None, None, None, None, None, None, None, None, None, None, None
+    dW, dbias = sn_backward(dwp, b.weight, rec, colsum, b.bias_ref)
+    return _conv_grads(dx, dW, dbias, dscale, dshift, d_ra, d_rb)
 
 
 # The whole backward of a 3x3 convolution with Cin = Cout = 16 / 32 on a large map in ONE launch (csrc/conv3x3_bwd.hip): effgrad on load + dgrad
 # with the prologue backward (ReLU mask / BatchNorm apply / 2x2 sum of an up-sampled source) in its store phase + wgrad + bias column sums
 # from the same LDS tiles (ExecOptions.fuse_3x3_backward; tests compare it with the separate launches).
-def _fused_3x3_eligible(ctx, dout, dstats):
-    rec = ctx.rec
-    o = opts_of(rec)
+def _fused_3x3_eligible(b, dout, dstats):
+    rec, o, need = b.rec, b.opts, b.need
     if not o.fuse_3x3_backward:
         return False
-    taps, rs, relu, Ca, ra_rs, nstride, Hc, Wc = ctx.cfg
-    need = ctx.needs_input_grad
-    has_bias, has_aff, has_ra, has_rb = ctx.has
-    res_out, res_in = ctx.links
-    x = ctx.saved_tensors[0]
-    N = x.shape[0]
-    if taps != 9 or rec.cin != rec.out or not need[0] or not need[1] or has_ra or has_rb or res_out is not None or res_in is not None:
+    if (b.taps != 9 or rec.cin != rec.out or not need[0] or not need[1] or b.has_ra or b.has_rb or b.res_out is not None
+            or b.res_in is not None):
         return False
-    if N * Hc * Wc < o.fuse_3x3_min_pixels or rec.kpad != rec.kpad2 or x.shape[3] != rec.cin:
+    if b.N * b.Hc * b.Wc < o.fuse_3x3_min_pixels or rec.kpad != rec.kpad2 or b.Cx != rec.cin:
         return False
-    if not H.lib().ieagan_conv3x3_bwd_supported(rec.cin, rs, int(has_aff), int(bool(relu)), int(dstats is not None), Hc, Wc):
+    if not H.lib().ieagan_conv3x3_bwd_supported(rec.cin, b.rs, int(b.has_aff), int(bool(b.relu)), int(dstats is not None), b.Hc, b.Wc):
         return False
-    if has_aff and ctx.events > 1 and nstride == 0:
+    if b.has_aff and b.events > 1 and b.nstride == 0:
         return False
-    st = dout.stride()
-    return dout.is_contiguous() or (st[3] == 1 and st[2] % 8 == 0 and st[2] >= rec.out and st[1] == Wc * st[2] and
-                                    st[0] == Hc * Wc * st[2] and dout.data_ptr() % 16 == 0)
+    return _row_stride(dout, rec.out, b.Hc, b.Wc) is not None
 
 
-def _conv3x3_backward_fused(ctx, dout, dstats):
-    x, weight, scale, shift, out = ctx.saved_tensors
-    rec = ctx.rec
-    taps, rs, relu, Ca, ra_rs, nstride, Hc, Wc = ctx.cfg
-    has_bias, has_aff, has_ra, has_rb = ctx.has
-    N, Hs, Ws, Cx = x.shape
-    C = rec.cin
-    dev = x.device
-    need = ctx.needs_input_grad
-    Cg = C if dout.is_contiguous() else dout.stride()[2]
+def _conv3x3_backward_fused(b, dout, dstats):
+    x, rec, need = b.x, b.rec, b.need
+    N, C, dev = b.N, b.Cin, b.dev
     eff = dstats is not None
     dstat = dstats[:, 0].contiguous() if eff else None
-    colsum = sn_scratch(rec, "b", (STAT_REPL, C), dev) if (has_bias and need[2]) else None
+    colsum = sn_scratch(rec, "b", (STAT_REPL, C), dev) if (b.has_bias and need[2]) else None
     dwp = sn_scratch(rec, "w", (C, rec.kpad), dev)
-    dx = torch.empty(N, Hs, Ws, C, dtype=BF16, device=dev)
-    d = H.Conv3x3BwdDesc(N, Hc, Wc, C, rec.kpad, H.src_desc(x, Cx, Hs, Ws, rs, scale, shift, nstride, relu), dout.data_ptr(), Cg,
-                         H.ptr(out) if eff else None, H.ptr(dstat), N // ctx.events, rec.w_bwd.data_ptr(), dx.data_ptr(), 16 if has_aff else None,
-                         dwp.data_ptr(), None, H.ptr(colsum), 0, 0)
-    ws = torch.empty(H.lib().ieagan_conv3x3_bwd_workspace(d), dtype=torch.float32, device=dev)
-    d.partials = ws.data_ptr()
-    acc = None
-    if has_aff:         # per-image BatchNorm accumulators: one slot per block of the image (single adder: bit-reproducible)
-        d.bn_slots = H.lib().ieagan_conv3x3_bwd_slots(d)
-        if d.bn_slots <= 0:
-            raise RuntimeError(f"ieagan_conv3x3_bwd_slots failed: {H.lib().ieagan_last_error().decode()}")
-        acc = zeros((N, d.bn_slots, 2, C), dev)
-        d.bn_acc = acc.data_ptr()
-    _fused_bwd_launch("ieagan_conv3x3_bwd", d, rec, ws, dwp, C, 9 * C, ())
-    dscale = dshift = None
-    if has_aff:
-        bn_link = getattr(scale, "_bn_link", None)
-        if bn_link is not None:
-            bn_link.acc = acc
-            dscale = dshift = _placeholder(scale)
-        else:                       # stand-alone use (tests): fold the replicated per-image accumulators here
-            sums = acc.sum(1)
-            dshift, dscale = sums[:, 0], sums[:, 1]
-            if nstride == 0:
-                dshift, dscale = dshift.sum(0), dscale.sum(0)
-    dW, dbias = sn_backward(dwp, weight, rec, colsum, ctx.bias_ref)
-    return dx, dW, dbias, dscale, dshift, None, None, None, None, None, None, None, None, None, None, None, None, None
+    dx = torch.empty(N, b.Hs, b.Ws, C, dtype=BF16, device=dev)
+    d = H.Conv3x3BwdDesc(N, b.Hc, b.Wc, C, rec.kpad, H.src_desc(x, b.Cx, b.Hs, b.Ws, b.rs, b.scale, b.shift, b.nstride, b.relu), dout.data_ptr(),
+                         _row_stride(dout, C, b.Hc, b.Wc), H.ptr(b.out) if eff else None, H.ptr(dstat), N // b.events, rec.w_bwd.data_ptr(),
+                         dx.data_ptr(), 16 if b.has_aff else None, dwp.data_ptr(), None, H.ptr(colsum), 0, 0)
+    acc, ws = _fused_buffers(d, "conv3x3_bwd", N, C, b.has_aff, dev)
+    _fused_bwd_launch("ieagan_conv3x3_bwd", d, rec, ws, dwp, C, 9 * C)
+    dscale, dshift = _bn_param_grads(b.scale, acc, b.nstride) if b.has_aff else (None, None)
+    dW, dbias = sn_backward(dwp, b.weight, rec, colsum, b.bias_ref)
+    return _conv_grads(dx, dW, dbias, dscale, dshift)
+
+
+# The generic backward of ``ConvFn``: separate launches, as four steps.
+def _out_gradient(b, dout, dstats):
+    """The out-gradient the other steps read -> (g, Cg, colsum, colsum_in_wgrad).  ``dout`` may be a channel slice of a wider NHWC tensor
+    (concat shortcut of a D block): the dgrad / wgrad kernels take a row stride, so only the statistics / effgrad / residual paths need a
+    packed copy.  With ``dstats`` the batch-statistics path of the following BN is folded in (g_eff).  ``colsum``: the bias column sums
+    [STAT_REPL, Cout], filled here unless ``colsum_in_wgrad`` leaves them to the weight-gradient launch."""
+    need, rec, Cout, dev = b.need, b.rec, b.Cout, b.dev
+    Cg = _row_stride(dout, Cout, b.Hc, b.Wc)
+    if (Cg is not None and dstats is None and not (b.has_bias and need[2] and not need[1]) and not (b.has_ra and need[5])
+            and not (b.has_rb and need[6])):
+        g = dout
+    else:
+        g, Cg = dout.contiguous(), Cout
+    P = b.N * b.Hc * b.Wc
+    colsum, colsum_in_wgrad = None, False
+    if dstats is not None:
+        geff = torch.empty_like(g)
+        if b.has_bias:
+            colsum = sn_scratch(rec, "b", (STAT_REPL, Cout), dev) if (need[1] and need[2]) else zeros((STAT_REPL, Cout), dev)
+        H.call("ieagan_effgrad", g.data_ptr(), b.out.data_ptr(), dstats[:, 0].contiguous().data_ptr(), geff.data_ptr(),
+               H.ptr(colsum), P, Cout, b.events, H.stream())
+        g = geff
+    elif b.has_bias and need[2]:
+        colsum = sn_scratch(rec, "b", (STAT_REPL, Cout), dev) if need[1] else zeros((STAT_REPL, Cout), dev)
+        if need[1]:
+            colsum_in_wgrad = True      # the wgrad kernel stages every g tile anyway: it takes the column sums along
+        else:
+            H.call("ieagan_effgrad", g.data_ptr(), None, None, None, colsum.data_ptr(), P, Cout, 1, H.stream())
+    return g, Cg, colsum, colsum_in_wgrad
+
+
+def _prologue_bwd(b, da, link, rmode):
+    """da (gradient w.r.t. the conv's activated, resampled input) -> (dx, dscale, dshift) through the stand-alone prologue backward,
+    which also adds the shortcut gradient ``link`` = (lg, lC, lCa) of mode ``rmode``."""
+    if rmode == 2:
+        raise RuntimeError("pooled shortcut gradient cannot be added by prologue_bwd")
+    dx = torch.empty(b.N, b.Hs, b.Ws, b.Cin, dtype=BF16, device=b.dev)
+    # per-image {sum d, sum d x} in one slot per block (single writer: bit-reproducible), folded by bn_finalize_bwd
+    acc = zeros((b.N, H.PROLOGUE_BWD_SLOTS, 2, b.Cin), b.dev) if b.has_aff else None
+    H.call("ieagan_prologue_bwd", da.data_ptr(), b.x.data_ptr(), b.Cx, H.ptr(b.scale), H.ptr(b.shift), b.nstride, int(b.relu),
+           b.rs, dx.data_ptr(), H.ptr(acc), None, b.N, b.Hs, b.Ws, b.Cin, H.ptr(link[0]), link[1], link[2], rmode,
+           H.PROLOGUE_BWD_SLOTS if b.has_aff else 0, H.stream())
+    return (dx,) + (_bn_param_grads(b.scale, acc, b.nstride) if b.has_aff else (None, None))
+
+
+def _data_gradient(b, g, Cg):
+    """-> (dx, dscale, dshift): one of four dgrad forms (+ ``prologue_bwd`` where the prologue backward does not fit the dgrad epilogue);
+    takes the shortcut gradient deposited in ``res_in`` along and serves a ``SumLink`` fan-in."""
+    x, scale, rs, relu, has_aff, res_in = b.x, b.scale, b.rs, b.relu, b.has_aff, b.res_in
+    N, Hs, Ws, Cin, dev = b.N, b.Hs, b.Ws, b.Cin, b.dev
+    dx = dscale = dshift = None
+    if not (b.need[0] or (has_aff and (b.need[3] or b.need[4]))):
+        return dx, dscale, dshift
+    da = torch.empty(N, b.Hc, b.Wc, Cin, dtype=BF16, device=dev)
+    fuse_mask = relu and not has_aff and rs == 0
+    plain = not relu and not has_aff
+    lg = lC = lCa = lmode = None
+    fan_in = res_in if isinstance(res_in, SumLink) else None
+    if res_in is not None and not res_in.ready:
+        res_in = None          # the shortcut operand needed no gradient (e.g. a detached block input) / first of a fan-in
+    if res_in is not None:
+        lg, lC, lCa, lmode = res_in.take()
+    link = (lg, lC or 0, lCa or 0)
+    bn_link = getattr(scale, "_bn_link", None) if has_aff else None
+    if (b.opts.fuse_bn_backward and has_aff and rs == 0 and bn_link is not None and (Hs * Ws) % 128 == 0 and Cin % 8 == 0
+            and (res_in is None or lmode in (0, 1))):
+        # BatchNorm apply + ReLU backward inside the dgrad epilogue: dx is written directly, the per-(n, c) sums go to
+        # replicated per-image accumulators that bn_finalize_bwd folds (no da tensor, no stand-alone pass over da / x)
+        dx = torch.empty(N, Hs, Ws, Cin, dtype=BF16, device=dev)
+        up = res_in is not None and lmode == 1          # shortcut gradient at double resolution: 2x2 SUM = 4 * average
+        acc = _dgrad(b, g, Cg, dx, link=link, link_rs=2 if up else 0, link_scale=4.0 if up else 1.0, mask=x, stats=True,
+                     bnb=(scale, b.shift, b.nstride, relu), flags=b.flags, npe=1)
+        dscale, dshift = _bn_param_grads(scale, acc, b.nstride)
+    elif res_in is not None and (fuse_mask or (plain and rs == 0)):
+        # bare-ReLU / no prologue (D blocks): the dgrad epilogue masks the main path and adds the
+        # shortcut gradient (0.25 * nearest-expand when the shortcut was average-pooled)
+        _dgrad(b, g, Cg, da, link=link, link_rs=1 if lmode == 2 else 0, link_scale=0.25 if lmode == 2 else 1.0,
+               mask=x if fuse_mask else None, flags=b.flags)
+        dx = da
+    elif res_in is not None and plain and rs == 2 and b.res_out is None:
+        # conv_sc of a D block (pooled, un-activated input): chain -- add the deposited shortcut
+        # gradient at the pooled resolution and re-deposit the sum for the block's first conv
+        _dgrad(b, g, Cg, da, link=link)
+        res_in.deposit(da, Cin, Cin, 2)
+    else:
+        _dgrad(b, g, Cg, da, mask=x if fuse_mask else None, flags=b.flags)
+        if (fuse_mask or (plain and rs == 0)) and res_in is None:
+            dx = da
+        else:
+            dx, dscale, dshift = _prologue_bwd(b, da, link, lmode if res_in is not None else 0)
+    if fan_in is not None:
+        if not (plain and rs == 0 and dx is da):
+            raise RuntimeError("a fan-in gradient link needs a plain same-resolution conv")
+        dx = fan_in.arrive(dx, Cin)
+    return dx, dscale, dshift
+
+
+def _weight_gradient(b, g, Cg, dwp, fork, colsum, colsum_in_wgrad):
+    """-> (dW, dbias).  ``dwp``: the zeroed accumulator (None: the weight is frozen, e.g. D in the G phase -- no launch at all);
+    ``fork``: the event the launch waits for on the weight-gradient side stream (None: it runs on the current stream)."""
+    x, rec, dev = b.x, b.rec, b.dev
+    want_bias = b.has_bias and b.need[2]
+    if dwp is None:
+        return None, (colsum.sum(0) if want_bias else None)
+    d = H.WgradDesc(b.N, b.Hc, b.Wc, b.Cin, b.Cout, b.taps, rec.kpad,
+                    H.src_desc(x, b.Cx, b.Hs, b.Ws, b.rs, b.scale, b.shift, b.nstride, b.relu), g.data_ptr(), Cg, dwp.data_ptr(), 0, 0, None,
+                    H.ptr(colsum) if colsum_in_wgrad else None)
+
+    def launch():
+        # large weight x many pixel splits: the blocks store partial slabs and a second launch folds them (two-stage
+        # accumulation; the float-atomic tail was the longest phase of these launches)
+        ws_n = H.lib().ieagan_conv_wgrad_workspace(d, 1) if b.opts.two_stage_wgrad else 0
+        if ws_n > 0:
+            ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
+            d.partials = ws.data_ptr()
+        H.call("ieagan_conv_wgrad", d, 1, H.stream())
+
+    if fork is not None:
+        side = wgrad_stream(dev)
+        with torch.cuda.stream(side):
+            side.wait_event(fork)
+            launch()
+        for t in (x, g, b.scale, b.shift):          # read by the side stream after this node has returned them to the pool
+            if t is not None:
+                t.record_stream(side)
+        rec.pass_.side = side
+    else:
+        launch()
+    return sn_backward(dwp, b.weight, rec, colsum if want_bias else None, b.bias_ref)
 
 
 class ConvFn(torch.autograd.Function):
@@ -959,173 +1080,23 @@ class ConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, dstats):
-        if _fused_1x1_eligible(ctx, dout, dstats):
-            return _conv1x1_backward_fused(ctx, dout, dstats)
-        if _fused_3x3_eligible(ctx, dout, dstats):
-            return _conv3x3_backward_fused(ctx, dout, dstats)
-        x, weight, scale, shift, out = ctx.saved_tensors
-        rec = ctx.rec
-        opts = opts_of(rec)
-        taps, rs, relu, Ca, ra_rs, nstride, Hc, Wc = ctx.cfg
-        has_bias, has_aff, has_ra, has_rb = ctx.has
-        res_out, res_in = ctx.links
-        N, Hs, Ws, Cx = x.shape
-        Cout, Cin = rec.out, rec.cin
-        dev = x.device
-        need = ctx.needs_input_grad
-        # The out-grad may be a channel slice of a wider NHWC tensor (concat shortcut of a D block): the dgrad / wgrad kernels
-        # take a row stride, so only the statistics / effgrad paths need a packed copy.
-        Cg = Cout
-        st = dout.stride()
-        sliced = (not dout.is_contiguous() and st[3] == 1 and st[2] % 8 == 0 and st[2] >= Cout and st[1] == Wc * st[2]
-                  and st[0] == Hc * Wc * st[2] and dout.data_ptr() % 16 == 0)
-        if sliced and dstats is None and not (has_bias and need[2] and not need[1]) and not (has_ra and need[5]) and not (has_rb and need[6]):
-            g, Cg = dout, st[2]
-        else:
-            g = dout.contiguous()
-        P = N * Hc * Wc
-        # ---- fold the batch-statistics path of the following BN into the out-grad; bias gradient
-        dbias = None
-        colsum_in_wgrad = False
-        if dstats is not None:
-            geff = torch.empty_like(g)
-            colsum = None
-            if has_bias:
-                colsum = sn_scratch(rec, "b", (STAT_REPL, Cout), dev) if (need[1] and need[2]) else zeros((STAT_REPL, Cout), dev)
-            H.call("ieagan_effgrad", g.data_ptr(), out.data_ptr(), dstats[:, 0].contiguous().data_ptr(), geff.data_ptr(),
-                   H.ptr(colsum), P, Cout, ctx.events, H.stream())
-            g = geff
-        elif has_bias and need[2]:
-            colsum = sn_scratch(rec, "b", (STAT_REPL, Cout), dev) if need[1] else zeros((STAT_REPL, Cout), dev)
-            if need[1]:
-                colsum_in_wgrad = True      # the wgrad kernel stages every g tile anyway: it takes the column sums along
-            else:
-                H.call("ieagan_effgrad", g.data_ptr(), None, None, None, colsum.data_ptr(), P, Cout, 1, H.stream())
-        # ---- residual operands
-        d_ra = d_rb = None
-        if has_ra and need[5]:
-            rshape = ctx.ra_shape
-            if res_out is not None:
-                res_out.deposit(g, Cout, Ca, ra_rs)            # consumed in-kernel by the block's first conv
-            elif ra_rs == 0:
-                if Ca == Cout and rshape[-1] == Cout:
-                    d_ra = g
-                else:
-                    d_ra = torch.zeros(rshape, dtype=BF16, device=dev)
-                    d_ra[..., :Ca] = g[..., :Ca]
-            else:
-                d_ra = torch.empty(rshape, dtype=BF16, device=dev)
-                H.call("ieagan_res_bwd", g.data_ptr(), Cout, d_ra.data_ptr(), rshape[-1], Ca, ra_rs, N, rshape[1], rshape[2],
-                       H.stream())
-        if has_rb and need[6]:
-            d_rb = g[..., Ca:]
+        b = _unpack(ctx)
+        if _fused_1x1_eligible(b, dout, dstats):
+            return _conv1x1_backward_fused(b, dout, dstats)
+        if _fused_3x3_eligible(b, dout, dstats):
+            return _conv3x3_backward_fused(b, dout, dstats)
+        g, Cg, colsum, colsum_in_wgrad = _out_gradient(b, dout, dstats)
+        d_ra, d_rb = _residual_grads(b, g)
         # ---- weight-gradient accumulator; fork point of the side stream (g and the zeroed accumulators are ready here)
         dwp = fork = None
-        if need[1]:
-            dwp = sn_scratch(rec, "w", (Cout, rec.kpad), dev)
-            if (opts.wgrad_side_stream and rec.deferred and d_ra is not g and d_rb is None):
+        if b.need[1]:
+            dwp = sn_scratch(b.rec, "w", (b.Cout, b.rec.kpad), b.dev)
+            if b.opts.wgrad_side_stream and b.rec.deferred and d_ra is not g and d_rb is None:
                 fork = torch.cuda.Event()
                 fork.record(torch.cuda.current_stream())
-        # ---- data gradient
-        dx = dscale = dshift = None
-        if need[0] or (has_aff and (need[3] or need[4])):
-            da = torch.empty(N, Hc, Wc, Cin, dtype=BF16, device=dev)
-            fuse_mask = relu and not has_aff and rs == 0
-            plain = not relu and not has_aff
-            lg = lC = lCa = lmode = None
-            fan_in = res_in if isinstance(res_in, SumLink) else None
-            if res_in is not None and not res_in.ready:
-                res_in = None          # the shortcut operand needed no gradient (e.g. a detached block input) / first of a fan-in
-            if res_in is not None:
-                lg, lC, lCa, lmode = res_in.take()
-            bn_link = getattr(scale, "_bn_link", None) if has_aff else None
-            if (opts.fuse_bn_backward and has_aff and rs == 0 and bn_link is not None and (Hs * Ws) % 128 == 0 and Cin % 8 == 0
-                    and (res_in is None or lmode in (0, 1))):
-                # BatchNorm apply + ReLU backward inside the dgrad epilogue: dx is written directly, the per-(n, c) sums go to
-                # replicated per-image accumulators that bn_finalize_bwd folds (no da tensor, no stand-alone pass over da / x)
-                dx = torch.empty(N, Hs, Ws, Cin, dtype=BF16, device=dev)
-                up = res_in is not None and lmode == 1          # shortcut gradient at double resolution: 2x2 SUM = 4 * average
-                acc = _conv_launch(g, Cg, Hc, Wc, 0, None, None, 0, False, N, Hc, Wc, Cout, Cin, taps, rec.kpad2, rec.w_bwd, None,
-                                   lg, lC or 0, lCa or 0, 2 if up else 0, None, 0, x, dx, True, ra_scale=4.0 if up else 1.0, npe=1,
-                                   bnb=(scale, shift, nstride, relu), flags=ctx.flags)
-                bn_link.acc = acc
-                dscale = dshift = _placeholder(scale)
-            elif res_in is not None and (fuse_mask or (plain and rs == 0)):
-                # bare-ReLU / no prologue (D blocks): the dgrad epilogue masks the main path and adds the
-                # shortcut gradient (0.25 * nearest-expand when the shortcut was average-pooled)
-                _conv_launch(g, Cg, Hc, Wc, 0, None, None, 0, False, N, Hc, Wc, Cout, Cin, taps, rec.kpad2, rec.w_bwd, None,
-                             lg, lC, lCa, 1 if lmode == 2 else 0, None, 0, x if fuse_mask else None, da, None,
-                             ra_scale=0.25 if lmode == 2 else 1.0, flags=ctx.flags)
-                dx = da
-            elif res_in is not None and plain and rs == 2 and res_out is None:
-                # conv_sc of a D block (pooled, un-activated input): chain -- add the deposited shortcut
-                # gradient at the pooled resolution and re-deposit the sum for the block's first conv
-                _conv_launch(g, Cg, Hc, Wc, 0, None, None, 0, False, N, Hc, Wc, Cout, Cin, taps, rec.kpad2, rec.w_bwd, None,
-                             lg, lC, lCa, 0, None, 0, None, da, None)
-                res_in.deposit(da, Cin, Cin, 2)
-                dx = None
-            else:
-                _conv_launch(g, Cg, Hc, Wc, 0, None, None, 0, False, N, Hc, Wc, Cout, Cin, taps, rec.kpad2, rec.w_bwd, None,
-                             None, 0, 0, 0, None, 0, x if fuse_mask else None, da, None, flags=ctx.flags)
-                if (fuse_mask or (plain and rs == 0)) and res_in is None:
-                    dx = da
-                else:
-                    dx = torch.empty(N, Hs, Ws, Cin, dtype=BF16, device=dev)
-                    acc = None
-                    if has_aff:     # per-image {sum d, sum d x} in one slot per block (single writer: bit-reproducible), folded by bn_finalize_bwd
-                        acc = zeros((N, H.PROLOGUE_BWD_SLOTS, 2, Cin), dev)
-                    rmode = 0
-                    if res_in is not None:
-                        if lmode == 2:
-                            raise RuntimeError("pooled shortcut gradient cannot be added by prologue_bwd")
-                        rmode = lmode
-                    H.call("ieagan_prologue_bwd", da.data_ptr(), x.data_ptr(), Cx, H.ptr(scale), H.ptr(shift), nstride, int(relu),
-                           rs, dx.data_ptr(), H.ptr(acc), None, N, Hs, Ws, Cin, H.ptr(lg), lC or 0, lCa or 0, rmode,
-                           H.PROLOGUE_BWD_SLOTS if has_aff else 0, H.stream())
-                    if has_aff:
-                        if bn_link is not None:
-                            bn_link.acc = acc
-                            dscale = dshift = _placeholder(scale)
-                        else:                       # stand-alone use (tests): fold the per-image slots here
-                            sums = acc.sum(1)
-                            dshift, dscale = sums[:, 0], sums[:, 1]
-                            if nstride == 0:
-                                dshift, dscale = dshift.sum(0), dscale.sum(0)
-            if fan_in is not None:
-                if not (plain and rs == 0 and dx is da):
-                    raise RuntimeError("a fan-in gradient link needs a plain same-resolution conv")
-                dx = fan_in.arrive(dx, Cin)
-        # ---- weight gradient (skipped entirely when the parameter is frozen, e.g. D in the G phase)
-        dW = None
-        if need[1]:
-            d = H.WgradDesc(N, Hc, Wc, Cin, Cout, taps, rec.kpad,
-                            H.src_desc(x, Cx, Hs, Ws, rs, scale, shift, nstride, relu), g.data_ptr(), Cg, dwp.data_ptr(), 0, 0, None,
-                            H.ptr(colsum) if colsum_in_wgrad else None)
-
-            def launch():
-                # large weight x many pixel splits: the blocks store partial slabs and a second launch folds them (two-stage
-                # accumulation; the float-atomic tail was the longest phase of these launches)
-                ws_n = H.lib().ieagan_conv_wgrad_workspace(d, int(opts.use_tr_read)) if opts.two_stage_wgrad else 0
-                if ws_n > 0:
-                    ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
-                    d.partials = ws.data_ptr()
-                H.call("ieagan_conv_wgrad", d, int(opts.use_tr_read), H.stream())
-
-            if fork is not None:
-                side = wgrad_stream(dev)
-                with torch.cuda.stream(side):
-                    side.wait_event(fork)
-                    launch()
-                for t in (x, g, scale, shift):          # read by the side stream after this node has returned them to the pool
-                    if t is not None:
-                        t.record_stream(side)
-                rec.pass_.side = side
-            else:
-                launch()
-            dW, dbias = sn_backward(dwp, weight, rec, colsum if (has_bias and need[2]) else None, ctx.bias_ref)
-        elif has_bias and need[2]:
-            dbias = colsum.sum(0)
-        return dx, dW, dbias, dscale, dshift, d_ra, d_rb, None, None, None, None, None, None, None, None, None, None, None
+        dx, dscale, dshift = _data_gradient(b, g, Cg)
+        dW, dbias = _weight_gradient(b, g, Cg, dwp, fork, colsum, colsum_in_wgrad)
+        return _conv_grads(dx, dW, dbias, dscale, dshift, d_ra, d_rb)
 
 
 def conv(x, weight, bias, rec, taps, *, scale=None, shift=None, relu=False, rs=0, ra=None, Ca=0, ra_rs=0, rb=None,
@@ -1216,26 +1187,23 @@ class DStemFn(torch.autograd.Function):
         lg, lC, lCa = dp0, 32, 32
         if ctx.link is not None and ctx.link.ready:
             lg, lC, lCa, _ = ctx.link.take()
+        if lg is None:
+            lC = lCa = 0
         # ---- conv_sc backward: d p0 = dsc Wsc + shortcut share (+ its weight / bias gradients)
-        st = dsc.stride()
-        Cg = 32 if dsc.is_contiguous() else st[2]
+        Cg = 32 if dsc.is_contiguous() else dsc.stride()[2]
         dpt = torch.empty(N, Hp, Wp, 32, dtype=BF16, device=dev)
         dWsc = dbsc = None
         if want_w:
             dwp = sn_scratch(recsc, "w", (32, recsc.kpad), dev)
             colsum = sn_scratch(recsc, "b", (STAT_REPL, 32), dev)
             d = H.Conv1x1BwdDesc(N, Hp, Wp, 32, 32, recsc.kpad, recsc.kpad2, H.src_desc(p0, 32, Hp, Wp, 0, None, None, 0, False), dsc.data_ptr(), Cg,
-                                 None, None, N, None, recsc.w_bwd.data_ptr(), H.ptr(lg), lC if lg is not None else 0, lCa if lg is not None else 0, 0,
-                                 dpt.data_ptr(), 1, None, dwp.data_ptr(), None, colsum.data_ptr(), opts_of(recsc).b1_flags, 0)
-            ws_n = H.lib().ieagan_conv1x1_bwd_workspace(d)
-            if ws_n > 0:
-                ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
-                d.partials = ws.data_ptr()
+                                 None, None, N, None, recsc.w_bwd.data_ptr(), H.ptr(lg), lC, lCa, 0,
+                                 dpt.data_ptr(), 1, None, dwp.data_ptr(), None, colsum.data_ptr(), 0, 0)
+            _, ws = _fused_buffers(d, "conv1x1_bwd", N, 32, False, dev)
             H.call("ieagan_conv1x1_bwd", d, H.stream())
             dWsc, dbsc = sn_backward(dwp, wsc, recsc, colsum, bsc)
         else:
-            _conv_launch(dsc, Cg, Hp, Wp, 0, None, None, 0, False, N, Hp, Wp, 32, 32, 1, recsc.kpad2, recsc.w_bwd, None, lg, lC if lg is not None else 0,
-                         lCa if lg is not None else 0, 0, None, 0, None, dpt, None)
+            _dgrad(types.SimpleNamespace(rec=recsc, N=N, Hc=Hp, Wc=Wp, Cout=32, Cin=32, taps=1), dsc, Cg, dpt, link=(lg, lC, lCa))
         dW_in = db_in = dW1 = db1 = dimg = None
         if want_w:
             dw_in = sn_scratch(rec_in, "w", (9, 32), dev)
@@ -1250,8 +1218,8 @@ class DStemFn(torch.autograd.Function):
         if need[0]:
             # the pass that trains G: d img = input_conv^T (dh1 W1 + 0.25 expand(d p0)) through the generic launches
             dh0 = torch.empty(N, Hh, Ww, 32, dtype=BF16, device=dev)
-            _conv_launch(dh1, 16, Hh, Ww, 0, None, None, 0, False, N, Hh, Ww, 16, 32, 1, rec1.kpad2, rec1.w_bwd, None, dpt, 32, 32, 1, None, 0, None,
-                         dh0, None, ra_scale=0.25)
+            _dgrad(types.SimpleNamespace(rec=rec1, N=N, Hc=Hh, Wc=Ww, Cout=16, Cin=32, taps=1), dh1, 16, dh0, link=(dpt, 32, 32), link_rs=1,
+                   link_scale=0.25)
             dimg = torch.empty(N, 1, Hh, Ww, dtype=torch.float32, device=dev)
             H.call("ieagan_conv_Cto1", dh0.data_ptr(), None, None, 0, 0, rec_in.w_plain.data_ptr(), None, dimg.data_ptr(), 0, N, Hh, Ww, 32, 1,
                    H.stream())
@@ -1362,14 +1330,6 @@ class ToNCHWFn(torch.autograd.Function):
         dx = torch.empty(N, Hh, Ww, C, dtype=BF16, device=g.device)
         H.call("ieagan_nchw_to_nhwc", g.contiguous().float().data_ptr(), dx.data_ptr(), None, N, C, Hh * Ww, 0, H.stream())
         return dx
-
-
-def channel_stats(x: torch.Tensor) -> torch.Tensor:
-    """(sum, sumsq) of a bf16 NHWC tensor (no autograd; for tensors not produced by a conv)."""
-    C = x.shape[-1]
-    st = new_stats(C, x.device)[0]
-    H.call("ieagan_channel_stats", x.data_ptr(), st.data_ptr(), x.numel() // C, C, H.stream())
-    return st
 
 
 # =====================================================================================================
