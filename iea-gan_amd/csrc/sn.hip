@@ -233,6 +233,8 @@ extern "C" int ieagan_sn_forward(const long* tab, const int* blocks, int nblocks
                                  float* params, float* ctx, float* part, void* pack, float eps, int training, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (nblocks <= 0) return 0;
+    CHECK_ARG(tab && blocks && cblocks && params && ctx && part && pack, "sn_forward: null pointer");
+    CHECK_ARG(ncblocks > 0, "sn_forward: nblocks=%d ncblocks=%d", nblocks, ncblocks);
     ProfScope prof("sn_forward", 0.0, 0.0, st);
     hipLaunchKernelGGL(sn_phase1_kernel, dim3(nblocks), dim3(256), 0, st, tab, blocks, (const float*)params, part);
     hipLaunchKernelGGL(sn_phase1b_kernel, dim3(ncblocks), dim3(256), 0, st, tab, cblocks, (const float*)part, ctx);
@@ -370,6 +372,9 @@ extern "C" int ieagan_sn_backward(const float* gsn, const float* W, int kind, in
     hipStream_t st = (hipStream_t)stream;
     CHECK_ARG(kind >= 0 && kind <= 3, "sn_backward: bad kind");
     CHECK_ARG(colsum == nullptr || dbias != nullptr, "sn_backward: colsum needs dbias");
+    CHECK_ARG(gsn && W && ctx && dW, "sn_backward: null pointer");
+    CHECK_ARG(out >= 1 && in >= 1, "sn_backward: out=%d in=%d", out, in);
+    CHECK_ARG(kind != 1 || (taps >= 1 && cin >= 1 && kpad >= taps * cin), "sn_backward: kind 1 with taps=%d cin=%d kpad=%d", taps, cin, kpad);
     ProfScope prof("sn_backward", 0.0, 0.0, st);
     if ((long)out * in <= 20000) {
         hipLaunchKernelGGL(sn_bwd_fused_kernel, dim3(1), dim3(1024), 0, st, gsn, W, kind, out, in, taps, cin, kpad, ctx, dW, accumulate,
@@ -484,6 +489,7 @@ extern "C" int ieagan_sn_backward_stack(const long* tab, const int* layers, cons
                                         void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (nlayers <= 0) return 0;
+    CHECK_ARG(tab && layers && row0 && dst && gst && params && ctx && grad_base, "sn_backward_stack: null pointer");
     ProfScope prof("sn_backward_stack", 0.0, 0.0, st);
     hipLaunchKernelGGL(sn_bwd_stack_kernel, dim3(nlayers), dim3(1024), 0, st, tab, layers, row0, dst, gst, params, ctx, grad_base, accumulate);
     CHECK_LAUNCH("sn_backward_stack");

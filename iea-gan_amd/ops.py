@@ -248,7 +248,8 @@ class SNBank:
 
     ``entries``: list of (name, kind, weight, u0, sv0) where the tensors are views into ``arena``.
     ``stack`` : names of kind-0 layers whose normalised weights must be laid out contiguously, in
-    this order, as one [sum(out), in] matrix (the 96 ccbn gain/bias linears of G)."""
+    this order, as one [sum(out), in] matrix (the 96 ccbn gain/bias linears of G): they are packed back to back,
+    so they must be kind 0 and share ``in`` (ValueError otherwise)."""
 
     ROWS = 32
 
@@ -270,7 +271,19 @@ class SNBank:
             assert d % 4 == 0 and 0 <= d < arena.numel() * 4, "SN tensors must live in the arena"
             return d // 4
 
-        order = list(stack) + [n for n in self.names if n not in set(stack)]
+        stack = list(stack)
+        if len(set(stack)) != len(stack) or any(n not in self.index for n in stack):
+            raise ValueError("SNBank: stack names must be distinct layers of the bank")
+        stack_in = None
+        for n in stack:       # run() hands the stack out as ONE [sum(out), in] fp32 matrix
+            _, kind, w, _, _ = entries[self.index[n]]
+            if kind != KIND_PLAIN:
+                raise ValueError(f"SNBank: stack layer {n!r} is kind {kind}, only kind-0 (plain fp32) layers can be stacked")
+            stack_in = w.numel() // w.shape[0] if stack_in is None else stack_in
+            if w.numel() // w.shape[0] != stack_in:
+                raise ValueError(f"SNBank: stack layer {n!r} has in = {w.numel() // w.shape[0]}, the stack's first layer has "
+                                 f"{stack_in}: the rows of one matrix share their length")
+        order = stack + [n for n in self.names if n not in set(stack)]
         self.stack_rows = {}
         srow = 0
         place = {}
@@ -292,10 +305,14 @@ class SNBank:
                 p1 = pack_off
                 nbytes = out * inn * 4
             place[n] = (p1, p2, kpad, kpad2, taps, cin, out, inn)
-            pack_off += (nbytes + 255) // 256 * 256
+            pack_off += nbytes
             if n in stack:
                 self.stack_rows[n] = (srow, out)
                 srow += out
+            # the stack layers lie back to back (one contiguous matrix, 16-byte aligned rows: in % 4 == 0 is the consumer's own condition);
+            # every other layer, and the first one after the stack, starts on a 256-byte boundary
+            if n not in stack or len(self.stack_rows) == len(stack):
+                pack_off = (pack_off + 255) // 256 * 256
         self.stack_total = srow
         for i, (n, kind, w, u, sv) in enumerate(entries):
             p1, p2, kpad, kpad2, taps, cin, out, inn = place[n]
