@@ -24,6 +24,7 @@ PXD_BINS = 251          # bins of the ADC spectrum of ieagan_pxd_stats (csrc/pxd
 PXD_CLUSTER_COLUMNS = {"size_spectrum": (0, 64), "charge_spectrum": (64, 256), "seed_spectrum": (320, 256), "size_u_spectrum": (576, 32),
                        "size_v_spectrum": (608, 32)}
 PXD_CLUSTER_BINS = 640
+PXD_MAP_U, PXD_MAP_V = 25, 48       # bins of the ieagan_pxd_cluster_maps grid over the rows / columns of a sensor (csrc/pxd_reco.hip)
 PROLOGUE_BWD_SLOTS = 64  # include/ieagan_hip.h: IEAGAN_PROLOGUE_BWD_SLOTS
 AUG_SLOTS = 128         # include/ieagan_hip.h: IEAGAN_AUG_SLOTS (per-image partial-sum slots of the DiffAugment entry points)
 BNB_REPL = 8            # replicas of the per-image accumulators of a BatchNorm-backward dgrad launch (common.h)
@@ -153,6 +154,9 @@ _SIGS = {
     "ieagan_pxd_clusters": [vp, vp, vp, i, i, i, l, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "ieagan_pxd_clusters_scratch": [i, i, i, l],
     "ieagan_pxd_cluster_stats": [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, l, vp, vp, vp],
+    "ieagan_pxd_cluster_positions": [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, l, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "ieagan_pxd_cluster_positions_scratch": [i, i, i, l],
+    "ieagan_pxd_cluster_maps": [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, l, vp, vp, vp, vp],
     "ieagan_ortho_ksplit": [],
     "ieagan_ortho_grad": [vp, vp, vp, vp, i, vp, i, vp, l, f, vp],
     "ieagan_selftest_tr_read": [vp, vp, vp],

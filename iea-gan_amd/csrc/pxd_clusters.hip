@@ -26,7 +26,6 @@
 #include "common.h"
 #include "pxd_common.h"
 
-#define CL_MAX_BLOCKS 1024          // one tile of the scan (pxd_common.h): 4 * CL_MAX_BLOCKS wave slots = 4 per thread of its workgroup
 #define CL_ACC 7                    // per-root accumulators: size, charge, seed, row min, row max, column min, column max
 
 #define CL_SIZE_BINS 64
@@ -34,16 +33,6 @@
 #define CL_SEED_BINS 256
 #define CL_EXTENT_BINS 32
 #define CL_COLUMNS (CL_SIZE_BINS + CL_CHARGE_BINS + CL_SEED_BINS + 2 * CL_EXTENT_BINS)
-
-static inline int cl_blocks(long cap) {
-    long b = (cap + 1023) / 1024;
-    if (b > CL_MAX_BLOCKS) b = CL_MAX_BLOCKS;
-    return (int)(b < 1 ? 1 : b);
-}
-static inline int cl_chunk(long cap, int B) {       // digits per wave, a multiple of 64
-    const long c = (cap + (long)B * PXD_WAVES - 1) / ((long)B * PXD_WAVES);
-    return (int)((c + 63) / 64 * 64 < 64 ? 64 : (c + 63) / 64 * 64);
-}
 
 __device__ __forceinline__ int cl_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -73,16 +62,6 @@ __device__ __forceinline__ void cl_union(int* parent, int a, int b) {
         if (old == a) return;           // a was a root and now hangs below b
         a = old;                        // a had a parent already: that parent and b are still to be joined
     }
-}
-
-__device__ __forceinline__ int cl_lower_bound(const int* __restrict__ a, int n, int v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_init_kernel(const int* __restrict__ dtotal, int cap, int* __restrict__ parent,

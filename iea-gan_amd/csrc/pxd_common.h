@@ -1,4 +1,4 @@
-// What the kernels over PXD sensor images share (pxd_stats.hip, pxd_digits.hip, pxd_clusters.hip): the launch partition, the walk
+// What the kernels over PXD sensor images share (pxd_stats.hip, pxd_digits.hip, pxd_clusters.hip, pxd_reco.hip): the launch partition, the walk
 // of a pixel range, the prefix sums, the row / column split and the launchers' argument checks.  Include after common.h.
 //
 // Launch partition: grid (P, N), workgroup (p, n) owns a contiguous pixel range of image n.
@@ -22,6 +22,19 @@ static inline int pxd_parts(int N, long HW) {
 }
 
 static inline int pxd_cap(long capacity) { return capacity > INT_MAX ? INT_MAX : (int)capacity; }
+
+// Launch partition of the kernels over a digit list or a cluster table of `cap` entries (pxd_clusters.hip, pxd_reco.hip): B workgroups,
+// wave g of the launch owns the entries [g * chunk, (g + 1) * chunk).
+#define CL_MAX_BLOCKS 1024          // one tile of the scan below: 4 * CL_MAX_BLOCKS wave slots = 4 per thread of its workgroup
+static inline int cl_blocks(long cap) {
+    long b = (cap + 1023) / 1024;
+    if (b > CL_MAX_BLOCKS) b = CL_MAX_BLOCKS;
+    return (int)(b < 1 ? 1 : b);
+}
+static inline int cl_chunk(long cap, int B) {       // digits per wave, a multiple of 64
+    const long c = (cap + (long)B * PXD_WAVES - 1) / ((long)B * PXD_WAVES);
+    return (int)((c + 63) / 64 * 64 < 64 ? 64 : (c + 63) / 64 * 64);
+}
 
 // Argument checks of the launchers, in front of the first launch; `who` is the launcher's name in the error text.  0 when they hold:
 //     if (int rc = pxd_check_geometry(...)) return rc;
@@ -113,6 +126,16 @@ __device__ __forceinline__ int pxd_scan_slots(int* __restrict__ slots, int group
         __syncthreads();                    // wsum is rewritten by the next tile; the bases written above are visible to this workgroup
     }
     return carry;
+}
+
+__device__ __forceinline__ int cl_lower_bound(const int* __restrict__ a, int n, int v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
 }
 
 // Flat pixel index -> row and column inside its image.

@@ -1,6 +1,7 @@
 """The PXD detector surface, this project's own (no counterpart in the reference's ``utils``): detector-level validation statistics
 (csrc/pxd_stats.hip), event production as sparse digits (csrc/pxd_digits.hip), clusters of the digits and their spectra
-(csrc/pxd_clusters.hip) and the event file of ``produce.py``.  ``utils`` re-exports every name defined here."""
+(csrc/pxd_clusters.hip), cluster reconstruction -- cuts, charge-weighted positions, per-sensor position maps (csrc/pxd_reco.hip) -- and the
+event file of ``produce.py``.  ``utils`` re-exports every name defined here."""
 from __future__ import annotations
 
 import numpy as np
@@ -375,6 +376,173 @@ def pxd_cluster_distance(real, fake):
     out = dict(cluster_rate_rel_err=_rel_err(r, np.asarray(fake["clusters"], np.float64).mean(0), r > 0))
     for name, key, width in (("size_w1", "size_spectrum", 1.0), ("cluster_charge_w1", "charge_spectrum", 8.0), ("seed_w1", "seed_spectrum", 1.0)):
         out[name] = _w1(real[key], fake[key], width)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# cluster reconstruction: seed / cluster-charge cuts, charge-weighted positions and per-sensor position maps (csrc/pxd_reco.hip)
+# ---------------------------------------------------------------------------------------------------------
+def _check_cuts(who, seed_cut, charge_cut):
+    seed_cut, charge_cut = int(seed_cut), int(charge_cut)
+    if seed_cut < 0 or charge_cut < 0:
+        raise ValueError(f"{who}: seed_cut = {seed_cut} / charge_cut = {charge_cut} is negative")
+    return seed_cut, charge_cut
+
+
+class PXDClusterPositions:
+    """Device-side result of ``pxd_cluster_positions``: the ``PXDClusters`` it came from (``clusters``), the moments ``mu`` / ``mv`` int64
+    ``[capacity]`` of every cluster (row j of the table: sum of charge x row, charge x column), and for the clusters that pass the cuts, in
+    cluster order: ``cluster`` int32 (row of the table), ``u`` / ``v`` fp32 (charge-weighted row / column in cell units, the centre of cell
+    ``r`` is ``r``), all ``[capacity]``; ``counts`` int32 ``[N]`` (accepted clusters per image), ``total`` int32 ``[1]``.  Only the first
+    ``clusters.total`` moments and the first ``total`` rows of ``cluster`` / ``u`` / ``v`` are written."""
+
+    def __init__(self, clusters, seed_cut, charge_cut, mu, mv, cluster, u, v, header):
+        self.clusters, self.capacity, self.n_sensors, self.shape = clusters, clusters.capacity, clusters.n_sensors, clusters.shape
+        self.seed_cut, self.charge_cut = seed_cut, charge_cut
+        self.mu, self.mv, self.cluster, self.u, self.v, self.header = mu, mv, cluster, u, v, header
+        self.counts, self.total = header[:self.shape[0]], header[self.shape[0]:]
+
+    def cpu(self):
+        """One read-back (every array packed into one device tensor, one copy, one wait) -> dict of NumPy arrays trimmed to the true
+        total, one entry per accepted cluster: ``cluster``, ``u``, ``v``, ``mu``, ``mv`` and, gathered through ``cluster``, ``sensor``,
+        ``event``, ``size``, ``charge``, ``seed``, ``size_u``, ``size_v``; plus ``counts [N]``.  Never truncated: when the digit total
+        exceeds the capacity, everything is run again with ``capacity = total`` (a second read-back, on that path only)."""
+        N, Hh, Ww = self.shape
+        c = self.clusters
+        d = c.digits
+        packed = torch.cat([d.header, c.header, self.header, self.cluster, self.u.view(torch.int32), self.v.view(torch.int32), c.first, c.size,
+                            c.charge, c.size_u, c.size_v, c.seed.to(torch.int32), self.mu.view(torch.int32), self.mv.view(torch.int32)]).cpu().numpy()
+        dtotal = int(packed[N])
+        counts, total = packed[2 * N + 2:3 * N + 2].copy(), int(packed[3 * N + 2])
+        if dtotal > self.capacity:
+            full = pxd_cluster_positions(d.images, d.threshold, self.seed_cut, self.charge_cut, capacity=dtotal, n_sensors=self.n_sensors)
+            for k in ("clusters", "capacity", "mu", "mv", "cluster", "u", "v", "header", "counts", "total"):
+                setattr(self, k, getattr(full, k))
+            return full.cpu()
+        C = self.capacity
+        col = lambda k: packed[3 * N + 3 + k * C:3 * N + 3 + (k + 1) * C]
+        wide = lambda k: packed[3 * N + 3 + k * C:3 * N + 3 + (k + 2) * C].view(np.int64)
+        cluster = col(0)[:total].copy()
+        image = col(3)[cluster] // np.int32(Hh * Ww)
+        return dict(cluster=cluster, u=col(1)[:total].view(np.float32).copy(), v=col(2)[:total].view(np.float32).copy(),
+                    mu=wide(9)[cluster], mv=wide(11)[cluster], sensor=(image % self.n_sensors).astype(np.int32),
+                    event=(image // self.n_sensors).astype(np.int32), size=col(4)[cluster], charge=col(5)[cluster], size_u=col(6)[cluster],
+                    size_v=col(7)[cluster], seed=col(8)[cluster].astype(np.uint8), counts=counts)
+
+
+def pxd_cluster_positions(images_or_clusters, threshold=0.0, seed_cut=0, charge_cut=0, capacity=None, n_sensors=40):
+    """Reconstructed clusters of a batch of sensor images ``[N, H, W]`` (fp32 or uint8 device tensor: ``pxd_clusters(images, threshold,
+    capacity, n_sensors)`` runs first) or of an existing ``PXDClusters`` (its threshold, capacity and sensors hold): the clusters with
+    ``seed >= seed_cut and charge >= charge_cut`` (integers in ADU; 0 accepts everything), in cluster order, with their charge-weighted
+    position ``u = sum(q * row) / sum(q)``, ``v = sum(q * column) / sum(q)`` (csrc/pxd_reco.hip).  The sums are exact 64-bit integers and
+    the division is one IEEE float64 division rounded to fp32, so ``(mu.astype(float64) / charge.astype(float64)).astype(float32)`` on the
+    host gives the same bits; bit-identical run to run.
+
+    Launches on the current stream, neither synchronises nor copies; with ``capacity`` given it can be captured into a HIP graph.  When
+    the digit total exceeds the capacity the device result covers the first ``capacity`` digits; ``PXDClusterPositions.cpu()`` reruns
+    instead of handing back a truncated event."""
+    H.require_gpu()
+    seed_cut, charge_cut = _check_cuts("pxd_cluster_positions", seed_cut, charge_cut)
+    c = images_or_clusters if isinstance(images_or_clusters, PXDClusters) else pxd_clusters(images_or_clusters, threshold, capacity, n_sensors)
+    d = c.digits
+    N, Hh, Ww = c.shape
+    dev, C = c.label.device, c.capacity
+    mu, mv = (torch.empty(C, dtype=torch.int64, device=dev) for _ in range(2))
+    cluster = torch.empty(C, dtype=torch.int32, device=dev)
+    u, v = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
+    header = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(H.lib().ieagan_pxd_cluster_positions_scratch(N, Hh, Ww, C), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        H.call("ieagan_pxd_cluster_positions", *_ptrs(C, d.index, d.charge, c.label), d.total.data_ptr(), *_ptrs(C, c.first, c.charge, c.seed),
+               c.total.data_ptr(), N, Hh, Ww, C, seed_cut, charge_cut, *_ptrs(C, mu, mv, cluster, u, v), header.data_ptr(),
+               header.data_ptr() + 4 * N, scratch.data_ptr(), H.stream())
+    return PXDClusterPositions(c, seed_cut, charge_cut, mu, mv, cluster, u, v, header)
+
+
+class PXDClusterMaps:
+    """Accumulator of per-sensor position maps of the reconstructed clusters over batches of sensor images in detector units (``[N, H, W]``
+    fp32 or uint8, image ``n`` is sensor ``n % n_sensors``), beside ``PXDClusterStatistics``: where on a sensor the clusters that pass the
+    cuts lie, on a fixed grid of 25 x 48 bins over the image.  ``update`` runs digits -> clusters -> positions ->
+    ``ieagan_pxd_cluster_maps`` on the current stream and neither synchronises nor copies; ``result()`` does the single read-back.
+    Counters are exact int64; the bin of a cluster is decided in integers.  ``capacity`` (digits per update) defaults to that of
+    ``pxd_digits``; an update whose digit total exceeds it is counted on the device and makes ``result()`` raise."""
+
+    def __init__(self, n_sensors=40, threshold=7.0, seed_cut=0, charge_cut=0, capacity=None, device=None):
+        self.n_sensors, self.threshold = int(n_sensors), float(threshold)
+        self.seed_cut, self.charge_cut = _check_cuts("PXDClusterMaps", seed_cut, charge_cut)
+        self.capacity = None if capacity is None else int(capacity)
+        self.device = torch.device(device) if device is not None else None
+        self.reset()
+
+    def reset(self):
+        self.tables = None              # int64 [2 * S * 25 * 48 + 1] on the device: count map, charge map, then the overflow counter
+        self.clusters, self.shape = [], None
+
+    def update(self, images):
+        x = _sensor_images(images, self.n_sensors, "pxd_digits", self.device)       # a wrong dtype or rank is reported as by pxd_digits
+        self.device = self.device or x.device
+        if self.shape not in (None, tuple(x.shape[1:])):
+            raise ValueError(f"PXDClusterMaps.update: image size {tuple(x.shape[1:])} differs from the accumulated {self.shape}")
+        self.shape = tuple(x.shape[1:])
+        p = pxd_cluster_positions(x, self.threshold, self.seed_cut, self.charge_cut, self.capacity, self.n_sensors)
+        c = p.clusters
+        N, Hh, Ww = p.shape
+        S, B = self.n_sensors, H.PXD_MAP_U * H.PXD_MAP_V
+        if self.tables is None:
+            self.tables = torch.zeros(2 * S * B + 1, dtype=torch.int64, device=self.device)
+        t = self.tables.data_ptr()
+        with torch.cuda.device(self.device):
+            H.call("ieagan_pxd_cluster_maps", *_ptrs(p.capacity, p.cluster), p.total.data_ptr(), *_ptrs(p.capacity, c.first, c.charge, p.mu, p.mv),
+                   c.total.data_ptr(), c.digits.total.data_ptr(), N, Hh, Ww, S, p.capacity, t, t + 8 * S * B, t + 16 * S * B, H.stream())
+        self.clusters.append(p.counts)
+        return p
+
+    def result(self):
+        """NumPy tables: int64 ``count_map`` / ``charge_map [S, 25, 48]`` (accepted clusters and their summed charge per bin
+        ``(floor(u / H * 25), floor(v / W * 48))``), ``u_profile [S, 25]`` and ``v_profile [S, 48]`` (sums of ``count_map`` over the other
+        axis), ``clusters`` int32 ``[events, S]`` (accepted clusters per image), ``n_events`` and ``shape`` (the image size ``(H, W)``,
+        which gives the bins their width in pixels).  Raises when an update overflowed."""
+        if not self.clusters:
+            raise RuntimeError("PXDClusterMaps.result() before any update()")
+        S, U, V = self.n_sensors, H.PXD_MAP_U, H.PXD_MAP_V
+        packed = torch.cat([self.tables, torch.cat(self.clusters).to(torch.int64)]).cpu().numpy()      # the one device-to-host copy
+        overflow = int(packed[2 * S * U * V])
+        if overflow != 0:
+            raise RuntimeError(f"PXDClusterMaps: {overflow} update(s) held more digits than the capacity"
+                               f"{'' if self.capacity is None else ' of %d' % self.capacity}, their clusters are truncated: "
+                               "pass a larger capacity= to PXDClusterMaps")
+        count_map = packed[:S * U * V].reshape(S, U, V).copy()
+        clusters = packed[2 * S * U * V + 1:].astype(np.int32).reshape(-1, S)
+        return dict(count_map=count_map, charge_map=packed[S * U * V:2 * S * U * V].reshape(S, U, V).copy(), u_profile=count_map.sum(2),
+                    v_profile=count_map.sum(1), clusters=clusters, n_events=int(clusters.shape[0]), shape=self.shape)
+
+
+def pxd_maps_accumulator(maps, **kw):
+    """The ``maps=`` keyword of ``train_fns.generated_statistics`` / ``validate.file_statistics``: None for False, else a ``PXDClusterMaps(**kw)``
+    without cuts (True) or with the cuts ``(seed_cut, charge_cut)``."""
+    if maps is False or maps is None:
+        return None
+    seed_cut, charge_cut = (0, 0) if maps is True else maps
+    return PXDClusterMaps(seed_cut=seed_cut, charge_cut=charge_cut, **kw)
+
+
+def pxd_map_distance(real, fake):
+    """Four distances between two ``PXDClusterMaps.result()`` tables (float64, host): ``accepted_rate_rel_err`` = mean over the sensors
+    with real accepted clusters of |fake - real| / real of the mean accepted clusters per image; ``u_profile_w1`` / ``v_profile_w1`` = 1-D
+    Wasserstein distances in pixels (bins ``H / 25`` and ``W / 48`` wide) between the row / column profiles pooled over the sensors and
+    normalised to 1, NaN when one side has no cluster at all; ``map_tv`` = mean over the sensors with real clusters of the total-variation
+    distance ``0.5 * sum |p_fake - p_real|`` between the normalised 25 x 48 maps (a fake sensor without a cluster counts as 1), NaN when no
+    sensor has a real cluster."""
+    Hh, Ww = real["shape"]
+    r = np.asarray(real["clusters"], np.float64).mean(0)
+    out = dict(accepted_rate_rel_err=_rel_err(r, np.asarray(fake["clusters"], np.float64).mean(0), r > 0),
+               u_profile_w1=_w1(real["u_profile"], fake["u_profile"], Hh / H.PXD_MAP_U),
+               v_profile_w1=_w1(real["v_profile"], fake["v_profile"], Ww / H.PXD_MAP_V))
+    mr = np.asarray(real["count_map"], np.float64).reshape(len(r), -1)
+    mf = np.asarray(fake["count_map"], np.float64).reshape(len(r), -1)
+    nr, nf = mr.sum(1), mf.sum(1)
+    tv = [0.5 * np.abs(mf[s] / nf[s] - mr[s] / nr[s]).sum() if nf[s] > 0 else 1.0 for s in np.nonzero(nr > 0)[0]]
+    out["map_tv"] = float(np.mean(tv)) if tv else float("nan")
     return out
 
 

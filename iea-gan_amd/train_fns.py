@@ -100,17 +100,19 @@ def test(G, D, G_ema, state_dict, config, test_log):
     test_log.log(itr=int(state_dict["itr"]), FID=float(FID))
 
 
-def generated_statistics(net, config, n_events, clusters=False):
+def generated_statistics(net, config, n_events, clusters=False, maps=False):
     """``utils.PXDStatistics`` over ``n_events`` events generated by ``net`` (eval mode when ``G_eval_mode``, no_grad, export epilogue).
     The latents and ``rdof`` come from a ``torch.Generator`` of its own seeded with ``config['seed']``: the global generators are not
     touched; the ``.training`` flags are restored.  No host synchronisation.  ``clusters=True``: the same events also go through a
-    ``utils.PXDClusterStatistics`` and ``(statistics, cluster statistics)`` is returned."""
+    ``utils.PXDClusterStatistics`` and ``(statistics, cluster statistics)`` is returned.  ``maps=True`` or ``maps=(seed_cut, charge_cut)``
+    (ADU): a ``utils.PXDClusterMaps`` with these cuts is fed as well and appended to the returned tuple."""
     dev = next(net.parameters()).device
     n = int(config["n_classes"])
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(config["seed"]))
     stats = utils.PXDStatistics(n_sensors=n, threshold=float(config["val_threshold"]), device=dev)
     cstats = utils.PXDClusterStatistics(n_sensors=n, threshold=float(config["val_threshold"]), device=dev) if clusters else None
+    mstats = utils.pxd_maps_accumulator(maps, n_sensors=n, threshold=float(config["val_threshold"]), device=dev)
     y = torch.arange(n, dtype=torch.long, device=dev)
     was_training = net.training
     if config["G_eval_mode"]:
@@ -124,9 +126,12 @@ def generated_statistics(net, config, n_events, clusters=False):
                 stats.update(x)
                 if clusters:
                     cstats.update(x)
+                if mstats is not None:
+                    mstats.update(x)
     finally:
         net.train(was_training)
-    return (stats, cstats) if clusters else stats
+    extra = tuple(a for a in (cstats, mstats) if a is not None)
+    return (stats,) + extra if extra else stats
 
 
 def validate(G, G_ema, real_stats, state_dict, config, log=None):

@@ -453,6 +453,40 @@ int ieagan_pxd_cluster_stats(const int* first, const int* size, const int* cchar
                              const int* size_v, const int* cluster_total, const int* digit_total, int N, int H, int W, int n_sensors,
                              long capacity, unsigned long long* tables, unsigned long long* overflow, void* stream);
 
+/* ---- cluster reconstruction: cuts, charge-weighted positions, per-sensor position maps (pxd_reco.hip) -------------
+ * Input: one ieagan_pxd_digits + ieagan_pxd_clusters result of a batch [N, H, W] (index / charge / label per digit, first / ccharge / seed
+ * per cluster, digit_total and cluster_total read on the device; every array [capacity]).  With M = min(*digit_total, capacity) digits and
+ * T = *cluster_total clusters:
+ *   mu [T], mv [T] uint64   moments of cluster j: sum of q_k * r_k and of q_k * c_k over its digits (row r, column c inside the image);
+ *                           64-bit integer atomics only: exact and order-independent
+ *   cluster j is ACCEPTED iff seed[j] >= seed_cut && ccharge[j] >= charge_cut (ADU; cuts of 0 accept everything).  Accepted cluster
+ *   number a, in cluster order, A in all:
+ *   cluster [A] int32       its row j of the cluster table
+ *   u [A], v [A] fp32       (float)((double)mu[j] / (double)ccharge[j]) and the same from mv: cell units, the centre of cell r is r.
+ *                           Numerator and denominator are exact and below 2^53 and the division is IEEE: the float64 recipe on the host
+ *                           gives the same bits.
+ *   counts [N] int32        accepted clusters per image (by `first`)            total [1] int32   A
+ * Nothing is written outside [0, T) of mu / mv and [0, A) of cluster / u / v; a batch without digits writes counts and total only
+ * (capacity 0: every [capacity] array may be NULL).  No atomic decides a position, no workgroup waits on another, no synchronise, no
+ * copy; the launch shapes depend on the capacity alone (graph-capturable).  Two calls on the same input write the same bytes.
+ * scratch: ieagan_pxd_cluster_positions_scratch(N, H, W, capacity) int32 words, need not be zeroed. */
+long ieagan_pxd_cluster_positions_scratch(int N, int H, int W, long capacity);
+int ieagan_pxd_cluster_positions(const int* index, const unsigned char* charge, const int* label, const int* digit_total,
+                                 const int* first, const int* ccharge, const unsigned char* seed, const int* cluster_total, int N,
+                                 int H, int W, long capacity, int seed_cut, int charge_cut, unsigned long long* mu,
+                                 unsigned long long* mv, int* cluster, float* u, float* v, int* counts, int* total, int* scratch,
+                                 void* stream);
+/* Position maps of the accepted clusters of one ieagan_pxd_cluster_positions result (cluster, accepted_total = its `total`, mu, mv),
+ * ACCUMULATED across calls (the caller zeroes them once): count [n_sensors][25][48] accepted clusters and charge [n_sensors][25][48] their
+ * summed charge, 64-bit unsigned, sensor = image of `first` modulo n_sensors (N a multiple of n_sensors), on a fixed grid of 25 x 48 bins over
+ * the image.  The bin is decided in 64-bit integers, no edge depends on float rounding:
+ *   bu = (mu * 25) / (ccharge * H)      bv = (mv * 48) / (ccharge * W)       i.e. floor(u / H * 25), inside the grid because u <= H - 1
+ * overflow [1] 64-bit unsigned: incremented when *digit_total > capacity, i.e. when the clusters come from a truncated digit list. */
+int ieagan_pxd_cluster_maps(const int* cluster, const int* accepted_total, const int* first, const int* ccharge,
+                            const unsigned long long* mu, const unsigned long long* mv, const int* cluster_total,
+                            const int* digit_total, int N, int H, int W, int n_sensors, long capacity, unsigned long long* count,
+                            unsigned long long* charge, unsigned long long* overflow, void* stream);
+
 /* ---- orthogonal regularisation (ortho.hip) -------------------------------------------------------
  * Replaces utils.ortho (reference utils/__init__.py:843-859) for ALL weight matrices of a network in one call:
  * grad[l] += 2*strength * ((W_l W_l^T) (.) (1 - I)) W_l, fp32, on the flat parameter / gradient arenas.
