@@ -44,13 +44,14 @@ __device__ __forceinline__ void xform8(float (&v)[8], const SrcDesc& s, int n, i
 // (XOR-swizzled columns): 16 stores + 64 / CPP loads per lane instead of a 16-value x log2(64 / CPP)-step shuffle
 // butterfly -- the flush was ~20 % of the instruction stream of the generator's 1x1 convolutions.
 #define STATS_SX_FLOATS (8 * 64)           // per wave (sums and sums of squares take turns)
-template <int NT, int NW = 4>
-__device__ __forceinline__ void stats_flush(const ConvArgs& a, float (&s1)[8], float (&s2)[8], int n_base, float* red /*[NW][NT*16][2]*/,
-                                            float* sx_all /* NW * STATS_SX_FLOATS, free at this point */, int replica, int event) {
+// stats_flush = stats_fold (every wave that holds partials: its row `wave` of red[]) -> block barrier -> stats_add (threads
+// 0 .. NT*16-1 of the block).  A kernel whose partials live in other waves than 0 .. NW-1 calls the two halves itself.
+template <int NT>
+__device__ __forceinline__ void stats_fold(float (&s1)[8], float (&s2)[8], float* red /*[NW][NT*16][2]*/, float* sx /* STATS_SX_FLOATS, private to this wave */,
+                                           int wave /* row of red[] */) {
     constexpr int CPP = NT * 2;
     constexpr int SH = 64 / CPP;                      // lanes sharing a chunk
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* sx = sx_all + wave * STATS_SX_FLOATS;
+    const int lane = threadIdx.x & 63;
     // wave-private matrix: LDS operations of one wave execute in order, no barrier needed between the phases
 #pragma unroll
     for (int w = 0; w < 2; ++w) {
@@ -68,7 +69,10 @@ __device__ __forceinline__ void stats_flush(const ConvArgs& a, float (&s1)[8], f
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // phase 1 overwrites what other lanes of this wave just read
         __builtin_amdgcn_wave_barrier();
     }
-    __syncthreads();
+}
+
+template <int NT, int NW = 4>
+__device__ __forceinline__ void stats_add(const ConvArgs& a, int n_base, const float* red /*[NW][NT*16][2]*/, int replica, int event) {
     const int t = threadIdx.x;
     if (t < NT * 16 && n_base + t < a.Cout) {
         float x1 = 0.f, x2 = 0.f;
@@ -84,6 +88,15 @@ __device__ __forceinline__ void stats_flush(const ConvArgs& a, float (&s1)[8], f
         atomicAdd(st + n_base + t, x1);
         atomicAdd(st + a.Cout + n_base + t, x2);
     }
+}
+
+template <int NT, int NW = 4>
+__device__ __forceinline__ void stats_flush(const ConvArgs& a, float (&s1)[8], float (&s2)[8], int n_base, float* red /*[NW][NT*16][2]*/,
+                                            float* sx_all /* NW * STATS_SX_FLOATS, free at this point */, int replica, int event) {
+    const int wave = threadIdx.x >> 6;
+    stats_fold<NT>(s1, s2, red, sx_all + wave * STATS_SX_FLOATS, wave);
+    __syncthreads();
+    stats_add<NT, NW>(a, n_base, red, replica, event);
 }
 
 
@@ -119,16 +132,11 @@ __device__ __forceinline__ void load_bias8(const ConvArgs& a, int n_base, float 
     }
 }
 
-template <bool BNBOK, int NT, int MTS = 2, bool EARLY = true, typename PixFn>
-__device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x4 (&acc)[MTS][NT], float* wlds, int n_base, PixFn pix,
-                                              float (&s1)[8], float (&s2)[8], const float* bias_pre = nullptr,
-                                              const bf16x8* mask_pre = nullptr) {
-    // bias_pre: this lane's 8 bias values (channel chunk lane % CPP), loaded once by a kernel that walks several tiles;
-    // mask_pre: the ReLU-mask / BatchNorm-input chunks of this call's (16*MTS*CPP)/64 iterations, requested by the caller ahead of
-    // time (same lane -> (row, chunk) mapping as below) so that their latency is not paid inside the epilogue.
+// conv_epilogue = conv_epilogue_put (accumulators -> the transpose buffer) + conv_epilogue_finish (everything else).  A kernel may run
+// the two halves in DIFFERENT waves (conv3x3_ws64: the MFMA waves put, the data-movement waves finish) with a block barrier between.
+template <int NT, int MTS = 2>
+__device__ __forceinline__ void conv_epilogue_put(const f32x4 (&acc)[MTS][NT], float* wlds) {
     constexpr int LDW = EpiLds<NT>::LDW;
-    constexpr int CPP = NT * 2;                         // 8-channel chunks per pixel
-    static_assert((16 * MTS * CPP) % 64 == 0, "epilogue rows x chunks must fill whole waves");
     const int lane = threadIdx.x & 63;
     const int lr = lane & 15, lg = lane >> 4;
 #pragma unroll
@@ -141,6 +149,21 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x4 (&a
     // (a block-wide barrier here made every wave wait for the slowest one four times per tile)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
+}
+
+template <bool BNBOK, int NT, int MTS = 2, bool EARLY = true, typename PixFn>
+__device__ __forceinline__ void conv_epilogue_finish(const ConvArgs& a, const float* wlds, int n_base, PixFn pix,
+                                                     float (&s1)[8], float (&s2)[8], const float* bias_pre = nullptr,
+                                                     const bf16x8* mask_pre = nullptr, const float* bnb_pre = nullptr) {
+    // bias_pre: this lane's 8 bias values (channel chunk lane % CPP), loaded once by a kernel that walks several tiles;
+    // mask_pre: the ReLU-mask / BatchNorm-input chunks of this call's (16*MTS*CPP)/64 iterations, requested by the caller ahead of
+    // time (same lane -> (row, chunk) mapping as below) so that their latency is not paid inside the epilogue;
+    // bnb_pre: LDS copy of the BatchNorm-backward scale / shift rows of the image all pixels of this call belong to
+    // ([0, NT*16) scale, [NT*16, 2*NT*16) shift of channels n_base ..), instead of four global loads per chunk.
+    constexpr int LDW = EpiLds<NT>::LDW;
+    constexpr int CPP = NT * 2;                         // 8-channel chunks per pixel
+    static_assert((16 * MTS * CPP) % 64 == 0, "epilogue rows x chunks must fill whole waves");
+    const int lane = threadIdx.x & 63;
     const int cc = lane % CPP;
     const int co0 = n_base + cc * 8;
     const bool ch_ok = co0 < a.Cout;
@@ -198,8 +221,15 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x4 (&a
             long mm;
             pix(row, mm, n, h, w);
             const long so = (long)n * a.bnb_nstride + co0;
-            const f32x4 sc0 = *(const f32x4*)(a.bnb_scale + so), sc1 = *(const f32x4*)(a.bnb_scale + so + 4);
-            const f32x4 sh0 = *(const f32x4*)(a.bnb_shift + so), sh1 = *(const f32x4*)(a.bnb_shift + so + 4);
+            f32x4 sc0, sc1, sh0, sh1;
+            if (bnb_pre != nullptr) {           // LDS-qualified reads (as a generic pointer they would be FLAT loads, see xform8)
+                typedef const __attribute__((address_space(3))) f32x4* lds_f32x4;
+                sc0 = *(lds_f32x4)(bnb_pre + cc * 8), sc1 = *(lds_f32x4)(bnb_pre + cc * 8 + 4);
+                sh0 = *(lds_f32x4)(bnb_pre + NT * 16 + cc * 8), sh1 = *(lds_f32x4)(bnb_pre + NT * 16 + cc * 8 + 4);
+            } else {
+                sc0 = *(const f32x4*)(a.bnb_scale + so), sc1 = *(const f32x4*)(a.bnb_scale + so + 4);
+                sh0 = *(const f32x4*)(a.bnb_shift + so), sh1 = *(const f32x4*)(a.bnb_shift + so + 4);
+            }
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const float xf = bf2f(xv[i]);
@@ -258,6 +288,14 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x4 (&a
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // the caller may overwrite the buffer (next half / next phase);
     __builtin_amdgcn_wave_barrier();                             // anything that touches ANOTHER wave's region needs a block barrier
+}
+
+template <bool BNBOK, int NT, int MTS = 2, bool EARLY = true, typename PixFn>
+__device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x4 (&acc)[MTS][NT], float* wlds, int n_base, PixFn pix,
+                                              float (&s1)[8], float (&s2)[8], const float* bias_pre = nullptr,
+                                              const bf16x8* mask_pre = nullptr) {
+    conv_epilogue_put<NT, MTS>(acc, wlds);
+    conv_epilogue_finish<BNBOK, NT, MTS, EARLY>(a, wlds, n_base, pix, s1, s2, bias_pre, mask_pre);
 }
 
 

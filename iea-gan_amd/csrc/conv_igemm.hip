@@ -551,7 +551,7 @@ static int launch_halo_pro(const ConvArgs& a, hipStream_t st) {
 
 int conv_gather_launch(const ConvArgs& a, hipStream_t st) {
     CHECK_ARG(a.taps == 1 || a.taps == 9, "conv: taps must be 1 or 9 (got %d)", a.taps);
-    CHECK_ARG((a.flags & ~(IEAGAN_CONV_FORCE_GATHER | IEAGAN_CONV_NO_LDS_WEIGHTS | IEAGAN_CONV_FP8 | IEAGAN_CONV_FP8_NOSCALE)) == 0, "conv: unknown flag bits 0x%x", a.flags);
+    CHECK_ARG((a.flags & ~(IEAGAN_CONV_FORCE_GATHER | IEAGAN_CONV_NO_LDS_WEIGHTS | IEAGAN_CONV_FP8 | IEAGAN_CONV_FP8_NOSCALE | IEAGAN_CONV_NO_WS64 | IEAGAN_CONV_FORCE_WS64)) == 0, "conv: unknown flag bits 0x%x", a.flags);
     CHECK_ARG(a.Cin % 8 == 0 && a.Cout % 8 == 0, "conv: Cin/Cout must be multiples of 8 (%d,%d)", a.Cin, a.Cout);
     CHECK_ARG(a.Kpad % 32 == 0 && a.Kpad >= a.taps * a.Cin, "conv: bad Kpad %d", a.Kpad);
     CHECK_ARG(a.src.rs >= 0 && a.src.rs <= 2, "conv: bad resample mode %d", a.src.rs);
@@ -586,7 +586,10 @@ int conv_gather_launch(const ConvArgs& a, hipStream_t st) {
     int rc;
     if (halo) {
         // C = 64 / 128: weights + halo resident in LDS (conv3x3_lds.hip); everything else: conv3x3_halo
-        rc = (a.flags & IEAGAN_CONV_NO_LDS_WEIGHTS) ? 0 : conv3x3_lds_launch(a, st);
+        // (C = 64 with enough tiles per persistent block: the wave-specialised form of the same LDS images, conv3x3_ws64.hip)
+        rc = (a.flags & IEAGAN_CONV_NO_LDS_WEIGHTS) ? 0 : conv3x3_ws64_launch(a, st);
+        if (rc < 0) return rc;
+        if (rc == 0) rc = (a.flags & IEAGAN_CONV_NO_LDS_WEIGHTS) ? 0 : conv3x3_lds_launch(a, st);
         if (rc < 0) return rc;
         // C = 16 / 32 on large maps: wave-specialised producer / consumer kernel (conv3x3_ws.hip)
         if (rc == 0 && !(a.flags & IEAGAN_CONV_NO_LDS_WEIGHTS)) rc = conv3x3_ws_launch(a, st);

@@ -16,10 +16,12 @@ aff = int(os.environ.get("CB_AFF", "0"))
 res = int(os.environ.get("CB_RES", "0"))          # 0 none, 1 same-res, 2 upsampled (half-res operand), 3 pooled (double-res operand)
 want_stats = int(os.environ.get("CB_STATS", "1"))
 flags = int(os.environ.get("CB_FLAGS", "0"))
-rs = int(os.environ.get("CB_RS", "0"))             # 2: the source lives at double resolution (2x2 average pool in the prologue)       # 1: force gather kernel, 2: conv3x3_halo instead of conv3x3_lds
+rs = int(os.environ.get("CB_RS", "0"))             # 1: the source lives at half resolution (nearest x2 up-sample), 2: at double resolution (2x2 average pool in the prologue)
+bnb = int(os.environ.get("CB_BNB", "0"))           # 1: BatchNorm-backward dgrad form (needs mask = 1; per-image accumulators, no bias)
+# CB_FLAGS: 1 gather kernel | 2 conv3x3_halo instead of conv3x3_lds | 16 conv3x3_lds instead of conv3x3_ws64 | 32 conv3x3_ws64 below its threshold too
 H.require_gpu()
 dev = "cuda:0"
-Hs, Ws = (2 * Hh, 2 * Ww) if rs == 2 else (Hh, Ww)
+Hs, Ws = (2 * Hh, 2 * Ww) if rs == 2 else (Hh // 2, Ww // 2) if rs == 1 else (Hh, Ww)
 x = torch.randn(N, Hs, Ws, Cin, device=dev).to(torch.bfloat16)
 kpad = ops._kpad(taps * Cin)
 w = (torch.randn(Cout, kpad, device=dev) * 0.05).to(torch.bfloat16)
@@ -27,6 +29,11 @@ bias = torch.randn(Cout, device=dev)
 out = torch.empty(N, Hh, Ww, Cout, device=dev, dtype=torch.bfloat16)
 mk = torch.randn(N, Hh, Ww, Cout, device=dev).to(torch.bfloat16) if mask else None
 stats = torch.zeros(32, 2, Cout, device=dev) if want_stats else None
+bsc = bsh = None
+if bnb:
+    stats = torch.zeros(N, 8, 2, Cout, device=dev)
+    bsc, bsh = 1 + 0.1 * torch.randn(N, Cout, device=dev), 0.1 * torch.randn(N, Cout, device=dev)
+    bias = None
 sc = (1 + 0.1 * torch.randn(N, Cin, device=dev)) if aff else None
 sh = (0.1 * torch.randn(N, Cin, device=dev)) if aff else None
 ra = None
@@ -41,7 +48,7 @@ elif res == 3:
 # the descriptor is built ONCE and the C entry point is called directly in the timed loop (see wgrad_bench.py)
 d = H.ConvDesc(N, Hh, Ww, Cin, Cout, taps, kpad, H.src_desc(x, Cin, Hs, Ws, rs, sc, sh, Cin if aff else 0, bool(relu)), H.ptr(w), H.ptr(bias),
                H.ptr(ra), Cout if ra is not None else 0, Cout if ra is not None else 0, max(res - 1, 0), 1.0, None, 0, H.ptr(mk), H.ptr(out),
-               H.ptr(stats), 0, flags, None, None, 0, 0)
+               H.ptr(stats), 1 if bnb else 0, flags, H.ptr(bsc), H.ptr(bsh), Cout if bnb else 0, int(bool(bnb)))
 fn = H.lib().ieagan_conv_forward
 st = H.stream()
 iters = max(iters, 200)
@@ -57,4 +64,4 @@ torch.cuda.synchronize()
 us = e0.elapsed_time(e1) * 1e3 / iters
 flops = 2.0 * N * Hh * Ww * Cout * taps * Cin
 byts = 2.0 * N * (Hs * Ws * Cin + Hh * Ww * Cout * (2 if mask else 1))
-print(f"conv {taps}tap N{N} {Hh}x{Ww} {Cin}->{Cout} relu{relu} mask{mask} aff{aff} res{res} rs{rs} stats{want_stats} flags{flags}: {us:.1f} us  {flops/us/1e6:.0f} TF  {byts/us/1e3:.0f} GB/s")
+print(f"conv {taps}tap N{N} {Hh}x{Ww} {Cin}->{Cout} relu{relu} mask{mask} aff{aff} res{res} rs{rs} bnb{bnb} stats{want_stats} flags{flags}: {us:.1f} us  {flops/us/1e6:.0f} TF  {byts/us/1e3:.0f} GB/s")
