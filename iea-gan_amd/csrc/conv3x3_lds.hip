@@ -11,28 +11,11 @@
 //     MFMAs), ONE round of persistent blocks; C = 128: 4 waves, 8x16 pixels x 32 couts -- small tiles because these layers live
 //     on 8x24 / 16x48 maps and need >= 256 blocks to fill the chip.
 // Prologue (per-(n,c) affine + ReLU, nearest x2 upsample of the source) and epilogue (bias, ReLU mask, residual, statistics,
-// BatchNorm-backward mode) are those of conv3x3_halo (shared code in conv_common.h).
+// BatchNorm-backward mode) are those of every 3x3 tile kernel (conv_common.h); the tile walk, the halo requests, the swizzle and the
+// K loop, which conv3x3_ws64 runs on the same images, are in conv3x3_tile.h.
 #include "common.h"
 #include "conv_args.h"
-#include "conv_common.h"
-
-// 16-byte chunk swizzle of an LDS image with CPR chunks per row.  Rows are CPR*16 bytes apart, so the 16 lanes of a fragment
-// read (same chunk of 16 consecutive rows) would hit only one or two of the sixteen 16-byte bank slots.  The chunk index is
-// XOR-ed with a per-row key:  CPR % 16 == 8 -> the row parity already selects one half of the slots, permute the low 3 chunk
-// bits with key = (r >> 1) & 7;  CPR % 16 == 0 -> permute 4 bits with key = r & 15.  `r` only has to enumerate the 16 rows of
-// a fragment read bijectively: the weight image uses the row index, the halo image the COLUMN of the pixel inside its halo row
-// (16 consecutive pixels of a row), which keeps every read address = per-lane register + compile-time immediate.
-// (CPR % 16 == 4, the fp8 images of 64-channel rows: two row bits select a quarter of the slots, key = (r >> 2) & 3 permutes 2 bits.)
-template <int CPR>
-__device__ __forceinline__ int swz_key(int r) {
-    static_assert(CPR % 16 == 8 || CPR % 16 == 0 || CPR % 16 == 4, "swizzle derived for rows of 4, 8 or 16 (mod 16) chunks");
-    return (CPR % 16 == 8) ? ((r >> 1) & 7) : (CPR % 16 == 4 ? ((r >> 2) & 3) : (r & 15));
-}
-template <int CPR>
-__device__ __forceinline__ int swz(int key, int chunk) {
-    constexpr int G = (CPR % 16 == 8) ? 8 : (CPR % 16 == 4 ? 4 : 16);
-    return (chunk & ~(G - 1)) | ((chunk ^ key) & (G - 1));
-}
+#include "conv3x3_tile.h"
 
 // LDS image of one block (weight slice + halo): above 80 KB only ONE block fits a CU, whatever the register budget says
 // (the halo region also carries the per-wave epilogue transpose buffers: sized for the larger of the two)
@@ -67,19 +50,8 @@ __global__ __launch_bounds__(NW * 64, (lds_image_bytes<CIN, NT, TH, TW, NW>() > 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 15, lg = lane >> 4;
     const int H = a.H, W = a.W;
-    // XCD-aware order, the n-tile column (C = 128: four blocks of 32 couts per tile range) as the fast index: the blocks that read
-    // the same halos run side by side on one XCD and share them through its L2 (conv1x1_stream.hip)
-    const int gy = (a.Cout + NT * 16 - 1) / (NT * 16);
-    int bid = blockIdx.x;
-    {
-        const int tot = nblk * gy, q = tot / 8, r = tot % 8, xcd = bid % 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
-    const int n_base = (bid % gy) * NT * 16;
-    bid /= gy;
-    const int event = bid / bpe;
-    const int t0 = event * tpe + (bid - event * bpe) * tpb;
-    const int t1 = min(t0 + tpb, (event + 1) * tpe);
+    const TileRun run = tile_run(nblk, (a.Cout + NT * 16 - 1) / (NT * 16), bpe, tpe, tpb);
+    const int n_base = run.column * NT * 16, t0 = run.t0, t1 = run.t1;
     if (t0 >= t1) return;
 
     // ---- weights -> LDS (swizzled), requested once per block
@@ -90,7 +62,7 @@ __global__ __launch_bounds__(NW * 64, (lds_image_bytes<CIN, NT, TH, TW, NW>() > 
             const int row = idx / WCH, kc = idx - row * WCH;
             bf16x8 v = zero8();
             if (n_base + row < a.Cout) v = *(const bf16x8*)((const bf16*)a.w + (long)(n_base + row) * a.Kpad + kc * 8);
-            *(bf16x8*)(wsm + (row * WCH + swz<WCH>(swz_key<WCH>(row), kc)) * 16) = v;
+            *(bf16x8*)(wsm + swz_offset<WCH>(row, row, kc)) = v;
         }
     }
     float s1[8], s2[8];
@@ -99,8 +71,7 @@ __global__ __launch_bounds__(NW * 64, (lds_image_bytes<CIN, NT, TH, TW, NW>() > 
     int aff_n = -1;
     // The raw halo of tile t+1 is requested into registers right before the K loop of tile t and written to LDS (prologue applied)
     // after tile t's epilogue: with one block per CU (117 / 120 KB of LDS) nothing else hides a tile's load latency.  The requests
-    // are unconditional (coordinates clamped into the image, the padding ring zeroed through a mask; past the block's last tile
-    // the last tile is requested again and dropped) so that the compiler can count what is in flight behind them.
+    // are the unconditional form (halo_request; past the block's last tile the last tile is requested again and dropped).
     // (C = 128: 16x48 29.7 -> 27.2 us, 8x24 20.3 -> 16.8 us.  C = 64 took this form in round 4 with the 8x32 tile: the 16x32 tile it
     //  replaced sat at the 256-register cap of an 8-wave block and spilled once the prefetch registers were added; 8x32 halves the
     //  accumulators -- 64x192 forward 63.6 -> 56.1 us, with BatchNorm prologue 70.8 -> 58.0, masked dgrad 73.1 -> 66.0 on one box.)
@@ -109,26 +80,11 @@ __global__ __launch_bounds__(NW * 64, (lds_image_bytes<CIN, NT, TH, TW, NW>() > 
     constexpr int HTOT = AH * AW * CH, HIT = XPF ? (HTOT + NTHR - 1) / NTHR : 1;
     bf16x8 rawn[HIT];
     unsigned okn = 0;
-    auto tile_of = [&](int t, int& n, int& h0, int& w0) {
-        n = t / (tiles_w * tiles_h);
-        const int trem = t - n * tiles_w * tiles_h;
-        h0 = (trem / tiles_w) * TH;
-        w0 = (trem % tiles_w) * TW;
-    };
+    auto tile_of = [&](int t, int& n, int& h0, int& w0) { tile_origin<TH, TW>(t, tiles_w, tiles_h, n, h0, w0); };
     auto request = [&](int t) {
         int n, h0, w0;
         tile_of(t, n, h0, w0);
-        okn = 0;
-#pragma unroll
-        for (int j = 0; j < HIT; ++j) {
-            const int idx = min((int)threadIdx.x + j * NTHR, HTOT - 1);
-            const int hp = idx / CH, cc = idx - hp * CH;
-            const int hh = h0 - 1 + hp / AW, ww = w0 - 1 + hp % AW;
-            const int hc = min(max(hh, 0), H - 1), wc = min(max(ww, 0), W - 1);
-            const int sh_ = (RS == 1) ? (hc >> 1) : hc, sw_ = (RS == 1) ? (wc >> 1) : wc;
-            rawn[j] = *(const bf16x8*)((const bf16*)a.src.x + (((long)n * a.src.Hs + sh_) * a.src.Ws + sw_) * a.src.Cx + cc * 8);
-            if ((int)threadIdx.x + j * NTHR < HTOT && hh >= 0 && hh < H && ww >= 0 && ww < W) okn |= 1u << j;
-        }
+        halo_request<RS, CH, AW, HTOT, NTHR>(a.src, H, W, n, h0, w0, threadIdx.x, rawn, okn);
     };
     if constexpr (XPF) request(t0);
     for (int t = t0; t < t1; ++t) {
@@ -147,22 +103,7 @@ __global__ __launch_bounds__(NW * 64, (lds_image_bytes<CIN, NT, TH, TW, NW>() > 
                 const int idx = threadIdx.x + j * NTHR;
                 if (idx >= HTOT) continue;
                 const int hp = idx / CH, cc = idx - hp * CH;
-                bf16x8 o = zero8();
-                if (okn & (1u << j)) {
-                    if (!AFF && RELU) {
-                        o = relu8(rawn[j]);
-                    } else if (AFF || RELU) {
-                        float v[8];
-    #pragma unroll
-                        for (int i = 0; i < 8; ++i) v[i] = bf2f(rawn[j][i]);
-                        xform8<AFF, RELU>(v, a.src, n, cc * 8, aff_s);
-    #pragma unroll
-                        for (int i = 0; i < 8; ++i) o[i] = f2bf(v[i]);
-                    } else {
-                        o = rawn[j];
-                    }
-                }
-                *(bf16x8*)(hsm + (hp * CH + swz<CH>(swz_key<CH>(hp % AW), cc)) * 16) = o;
+                *(bf16x8*)(hsm + swz_offset<CH>(hp, hp % AW, cc)) = prologue_chunk<AFF, RELU>(rawn[j], okn & (1u << j), aff_s + cc * 8, aff_s + AFF_MAXC + cc * 8);
             }
         } else {
         // ---- halo -> LDS with the prologue applied: batches of SB independent loads per thread
@@ -179,8 +120,7 @@ __global__ __launch_bounds__(NW * 64, (lds_image_bytes<CIN, NT, TH, TW, NW>() > 
                         const int hp = idx / CH, cc = idx - hp * CH;
                         const int hh = h0 - 1 + hp / AW, ww = w0 - 1 + hp % AW;
                         if (hh >= 0 && hh < H && ww >= 0 && ww < W) {
-                            const int sh_ = (RS == 1) ? (hh >> 1) : hh, sw_ = (RS == 1) ? (ww >> 1) : ww;
-                            rawb[j] = *(const bf16x8*)((const bf16*)a.src.x + (((long)n * a.src.Hs + sh_) * a.src.Ws + sw_) * a.src.Cx + cc * 8);
+                            rawb[j] = *halo_src_chunk<RS>(a.src, n, hh, ww, cc);
                             okb |= 1u << j;
                         }
                     }
@@ -189,22 +129,7 @@ __global__ __launch_bounds__(NW * 64, (lds_image_bytes<CIN, NT, TH, TW, NW>() > 
                         const int idx = threadIdx.x + (b0 + j) * NTHR;
                         if (b0 + j >= ITERS || idx >= TOT) continue;
                         const int hp = idx / CH, cc = idx - hp * CH;
-                        bf16x8 o = zero8();
-                        if (okb & (1u << j)) {
-                            if (!AFF && RELU) {
-                                o = relu8(rawb[j]);
-                            } else if (AFF || RELU) {
-                                float v[8];
-    #pragma unroll
-                                for (int i = 0; i < 8; ++i) v[i] = bf2f(rawb[j][i]);
-                                xform8<AFF, RELU>(v, a.src, n, cc * 8, aff_s);
-    #pragma unroll
-                                for (int i = 0; i < 8; ++i) o[i] = f2bf(v[i]);
-                            } else {
-                                o = rawb[j];
-                            }
-                        }
-                        *(bf16x8*)(hsm + (hp * CH + swz<CH>(swz_key<CH>(hp % AW), cc)) * 16) = o;
+                        *(bf16x8*)(hsm + swz_offset<CH>(hp, hp % AW, cc)) = prologue_chunk<AFF, RELU>(rawb[j], okb & (1u << j), aff_s + cc * 8, aff_s + AFF_MAXC + cc * 8);
                     }
                 }
             }
@@ -213,109 +138,39 @@ __global__ __launch_bounds__(NW * 64, (lds_image_bytes<CIN, NT, TH, TW, NW>() > 
         if constexpr (XPF) request(min(t + 1, t1 - 1));  // in flight during the K loop and the epilogue below
         // ---- K loop from LDS: wave owns m-tiles [wave*MTW, +MTW) (tile row mt / MPR, columns (mt % MPR)*16 ..)
         f32x4 acc[MTW][NT];
-#pragma unroll
-        for (int m = 0; m < MTW; ++m)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[m][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // Fragment addresses = per-lane register (swizzled chunk offset) + immediate (tap / k-step / n-tile displacement):
-        //   A: pixel (row mt/MPR + dy, col (mt%MPR)*16 + lr + dx) of the halo, chunk cq*4 + lg of its CIN/8 chunks
-        //   B: weight row nt*16 + lr, chunk ks*4 + lg
-        constexpr int NV = CH / 4;          // swizzle variants of the chunk index (CIN / 32)
-        int offA[MTW][3][NV];
-#pragma unroll
-        for (int m = 0; m < MTW; ++m) {
-            const int mt = wave * MTW + m;
-            const int col = (mt % MPR) * 16 + lr;
-            const int base = ((mt / MPR) * AW + col) * CH * 16;
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-                for (int v = 0; v < NV; ++v) offA[m][dx][v] = base + swz<CH>(swz_key<CH>(col + dx), v * 4 + lg) * 16;
-        }
-        int offB[NV];
-#pragma unroll
-        for (int v = 0; v < NV; ++v) offB[v] = lr * WCH * 16 + swz<WCH>(swz_key<WCH>(lr), v * 4 + lg) * 16;
-        auto lda = [&](int ks, bf16x8(&x)[MTW]) {
-            const int tap = (ks * 32) / CIN, cq = ((ks * 32) % CIN) / 32;
-            const int imm = ((tap / 3) * AW + (tap % 3)) * CH * 16;
-#pragma unroll
-            for (int m = 0; m < MTW; ++m) x[m] = *(const bf16x8*)(hsm + offA[m][tap % 3][cq] + imm);
-        };
-        auto ldb = [&](int ks, bf16x8(&b)[NT]) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) b[nt] = *(const bf16x8*)(wsm + offB[ks % NV] + nt * 16 * WCH * 16 + (ks / NV) * NV * 64);
-        };
-        bf16x8 aq[2][MTW], bq[2][NT];
-        lda(0, aq[0]);
-        ldb(0, bq[0]);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            if (ks + 1 < KS) {
-                lda(ks + 1, aq[(ks + 1) & 1]);
-                ldb(ks + 1, bq[(ks + 1) & 1]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int m = 0; m < MTW; ++m)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ks & 1][m], bq[ks & 1][nt], acc[m][nt], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        int offA[MTW][3][CIN / 32], offB[CIN / 32];
+        lds_frag_offsets<CIN, MTW, MPR, AW>(wave * MTW, lr, lg, offA, offB);
+        kloop_swizzled<CIN, NT, MTW, AW>(hsm, wsm, offA, offB, acc);
         __syncthreads();              // halo consumed: its LDS becomes the per-wave epilogue transpose buffers
         float* epi = (float*)hsm + wave * EpiLds<NT>::FLOATS;
 #pragma unroll
         for (int half = 0; half < MTW / 2; ++half) {
-            const int mt = wave * MTW + 2 * half;          // two m-tiles: 32 consecutive pixels of one tile row when MPR == 2,
-            auto pix = [&](int row, long& m, int& nn, int& h, int& w) -> bool {     // one m-tile of each of two rows when MPR == 1
-                const int mtt = mt + (row >> 4);
-                nn = n;
-                h = h0 + mtt / MPR;
-                w = w0 + (mtt % MPR) * 16 + (row & 15);
-                m = ((long)n * H + h) * W + w;
-                return FULL ? true : (h < H && w < W);
-            };
+            const tile_pix<MPR, FULL> pix(n, h0, w0, wave * MTW + 2 * half, H, W);
             const f32x4(&sub)[2][NT] = *reinterpret_cast<const f32x4(*)[2][NT]>(&acc[2 * half]);
             conv_epilogue<BNB, NT, 2, false>(a, sub, epi, n_base, pix, s1, s2);
         }
     }
     if (a.stats != nullptr) {
         __syncthreads();
-        stats_flush<NT, NW>(a, s1, s2, n_base, red, (float*)hsm, bid, event);
+        stats_flush<NT, NW>(a, s1, s2, n_base, red, (float*)hsm, run.bid, run.event);
     }
 }
 
 template <bool AFF, bool RELU, int RS, bool BNB>
 static int lds_launch(const ConvArgs& a, hipStream_t st) {
-    const int n_events = (a.stats != nullptr && a.n_per_event > 0) ? a.N / a.n_per_event : 1;
 #define LDS_LAUNCH(CINV, NTV, THV, TWV, NWV)                                                                                       \
     {                                                                                                                              \
-        const int tiles_w = (a.W + TWV - 1) / TWV, tiles_h = (a.H + THV - 1) / THV;                                                \
-        const int ntiles = a.N * tiles_w * tiles_h;                                                                                \
-        const int tpe = ntiles / n_events;                                                                                         \
         const int gy = (a.Cout + 16 * NTV - 1) / (16 * NTV);                                                                       \
         /* ONE round of persistent blocks (one or two per CU, by the LDS image): a block loads its weight slice once and keeps the \
            next tile's halo in flight while it computes */                                                                         \
-        const int slots = 256 * (lds_image_bytes<CINV, NTV, THV, TWV, NWV>() > 80 * 1024 ? 1 : 2);                \
-        int tpb = (ntiles * gy + slots - 1) / slots;                                                                               \
-        if (tpb < 1) tpb = 1;                                                                                                      \
-        if (tpb > tpe) tpb = tpe;                                                                                                  \
-        const int bpe = (tpe + tpb - 1) / tpb;                                                                                     \
-        const int nblk = bpe * n_events;                                                                                           \
-        CONV_PLAN_POINT(bpe, 1)                                                                                                    \
-        const size_t lds = (size_t)lds_image_bytes<CINV, NTV, THV, TWV, NWV>();                             \
+        const size_t lds = (size_t)lds_image_bytes<CINV, NTV, THV, TWV, NWV>();                                                    \
+        const TilePlan p = tile_plan(a, THV, TWV, gy, 256 * (lds > 80 * 1024 ? 1 : 2));                                            \
+        CONV_PLAN_POINT(p.bpe, 1)                                                                                                  \
+        constexpr auto kfull = conv3x3_lds_kernel<AFF, RELU, RS, CINV, NTV, THV, TWV, NWV, BNB, true>;                             \
+        constexpr auto kpart = conv3x3_lds_kernel<AFF, RELU, RS, CINV, NTV, THV, TWV, NWV, BNB, false>;                            \
         const bool full = a.H % THV == 0 && a.W % TWV == 0;                                                                        \
-        auto kern = full ? conv3x3_lds_kernel<AFF, RELU, RS, CINV, NTV, THV, TWV, NWV, BNB, true>                                  \
-                         : conv3x3_lds_kernel<AFF, RELU, RS, CINV, NTV, THV, TWV, NWV, BNB, false>;                                \
-        static bool attr_set[2] = {false, false};                                                                                  \
-        if (!attr_set[full]) {                                                                                                     \
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {      \
-                ieagan_set_error("conv3x3_lds: cannot reserve %zu bytes of LDS", lds);                                             \
-                return IEAGAN_ELAUNCH;                                                                                             \
-            }                                                                                                                      \
-            attr_set[full] = true;                                                                                                 \
-        }                                                                                                                          \
-        hipLaunchKernelGGL(kern, dim3(nblk * gy), dim3(NWV * 64), lds, st, a, tiles_w, tiles_h, tpe, tpb, nblk, bpe);               \
+        if ((full ? reserve_lds<kfull>(lds, "conv3x3_lds") : reserve_lds<kpart>(lds, "conv3x3_lds")) != 0) return IEAGAN_ELAUNCH;  \
+        hipLaunchKernelGGL(full ? kfull : kpart, dim3(p.nblk * gy), dim3(NWV * 64), lds, st, a, p.tiles_w, p.tiles_h, p.tpe, p.tpb, p.nblk, p.bpe); \
         return 1;                                                                                                                  \
     }
     // C = 64 on the smallest maps (16x48: 80 tile pairs): the 8-wave blocks would cover a third of the CUs -- the 4-wave 8x16 form with
@@ -396,17 +251,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_lds_fp8_kernel(ConvArgs a,
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 15, lg = lane >> 4;
     const int H = a.H, W = a.W;
-    const int gy = (a.Cout + NT * 16 - 1) / (NT * 16);         // n-tile column = fast index of the XCD-aware order (see the bf16 kernel)
-    int bid = blockIdx.x;
-    {
-        const int tot = nblk * gy, q = tot / 8, r = tot % 8, xcd = bid % 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
-    const int n_base = (bid % gy) * NT * 16;
-    bid /= gy;
-    const int event = bid / bpe;
-    const int t0 = event * tpe + (bid - event * bpe) * tpb;
-    const int t1 = min(t0 + tpb, (event + 1) * tpe);
+    const TileRun run = tile_run(nblk, (a.Cout + NT * 16 - 1) / (NT * 16), bpe, tpe, tpb);
+    const int n_base = run.column * NT * 16, t0 = run.t0, t1 = run.t1;
     if (t0 >= t1) return;
 
     // ---- weights: bf16 pack -> amax of the block's slice -> e4m3 image in LDS
@@ -446,7 +292,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_lds_fp8_kernel(ConvArgs a,
                 float v[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) v[i] = bf2f(wr[j][i]);
-                *(i64*)(wsm + (row * WCH + swz<WCH>(swz_key<WCH>(row), kc >> 1)) * 16 + (kc & 1) * 8) = pack_fp8x8(v, sw);
+                *(i64*)(wsm + swz_offset<WCH>(row, row, kc >> 1) + (kc & 1) * 8) = pack_fp8x8(v, sw);
             }
         }
     }
@@ -455,9 +301,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_lds_fp8_kernel(ConvArgs a,
     for (int i = 0; i < 8; ++i) s1[i] = s2[i] = 0.f;
     int aff_n = -1;
     for (int t = t0; t < t1; ++t) {
-        const int n = t / (tiles_w * tiles_h);
-        const int trem = t - n * tiles_w * tiles_h;
-        const int h0 = (trem / tiles_w) * TH, w0 = (trem % tiles_w) * TW;
+        int n, h0, w0;
+        tile_origin<TH, TW>(t, tiles_w, tiles_h, n, h0, w0);
         if (AFF && n != aff_n) {
             __syncthreads();
             stage_aff(aff_s, a.src, n, CIN);
@@ -477,8 +322,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_lds_fp8_kernel(ConvArgs a,
                 const int hh = h0 - 1 + hp / AW, ww = w0 - 1 + hp % AW;
                 if (!(hh >= 0 && hh < H && ww >= 0 && ww < W)) return zero8();
                 ok = true;
-                const int sh_ = (RS == 1) ? (hh >> 1) : hh, sw_ = (RS == 1) ? (ww >> 1) : ww;
-                return *(const bf16x8*)((const bf16*)a.src.x + (((long)n * a.src.Hs + sh_) * a.src.Ws + sw_) * a.src.Cx + cc * 8);
+                return *halo_src_chunk<RS>(a.src, n, hh, ww, cc);
             };
             auto xf = [&](int j, const bf16x8& raw, bool ok, float (&v)[8]) {
                 const int idx = threadIdx.x + j * NTHR;
@@ -515,7 +359,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_lds_fp8_kernel(ConvArgs a,
                     const int hp = idx / (CIN / 8), cc = idx - hp * (CIN / 8);
                     float v[8];
                     xf(j0 + j, rawb[j], okb[j], v);
-                    *(i64*)(hsm + (hp * CH + swz<CH>(swz_key<CH>(hp % AW), cc >> 1)) * 16 + (cc & 1) * 8) = pack_fp8x8(v, sa);
+                    *(i64*)(hsm + swz_offset<CH>(hp, hp % AW, cc >> 1) + (cc & 1) * 8) = pack_fp8x8(v, sa);
                 }
             }
         }
@@ -651,39 +495,24 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_lds_fp8_kernel(ConvArgs a,
         float* epi = (float*)hsm + wave * EpiLds<NT>::FLOATS;
 #pragma unroll
         for (int half = 0; half < MTW / 2; ++half) {
-            const int mt = wave * MTW + 2 * half;
-            auto pix = [&](int row, long& m, int& nn, int& h, int& w) -> bool {
-                const int mtt = mt + (row >> 4);
-                nn = n;
-                h = h0 + mtt / MPR;
-                w = w0 + (mtt % MPR) * 16 + (row & 15);
-                m = ((long)n * H + h) * W + w;
-                return h < H && w < W;
-            };
+            const tile_pix<MPR, false> pix(n, h0, w0, wave * MTW + 2 * half, H, W);
             const f32x4(&sub)[2][NT] = *reinterpret_cast<const f32x4(*)[2][NT]>(&acc[2 * half]);
             conv_epilogue<BNB, NT, 2, false>(a, sub, epi, n_base, pix, s1, s2);
         }
     }
     if (a.stats != nullptr) {
         __syncthreads();
-        stats_flush<NT, NW>(a, s1, s2, n_base, red, (float*)hsm, bid, event);
+        stats_flush<NT, NW>(a, s1, s2, n_base, red, (float*)hsm, run.bid, run.event);
     }
 }
 
 template <bool AFF, bool RELU, int RS, bool BNB = false>
 static int lds_fp8_launch(const ConvArgs& a, hipStream_t st) {
-    const int n_events = (a.stats != nullptr && a.n_per_event > 0) ? a.N / a.n_per_event : 1;
 #define F8_LAUNCH(CINV, NTV, THV, TWV, NWV)                                                                                        \
     {                                                                                                                              \
-        const int tiles_w = (a.W + TWV - 1) / TWV, tiles_h = (a.H + THV - 1) / THV;                                                \
-        const int ntiles = a.N * tiles_w * tiles_h;                                                                                \
-        const int tpe = ntiles / n_events;                                                                                         \
         const int gy = (a.Cout + 16 * NTV - 1) / (16 * NTV);                                                                       \
-        int tpb = (ntiles * gy + 1023) / 1024;          /* two resident blocks per CU */                                           \
-        if (tpb < 1) tpb = 1;                                                                                                      \
-        if (tpb > tpe) tpb = tpe;                                                                                                  \
-        const int bpe = (tpe + tpb - 1) / tpb;                                                                                     \
-        const int nblk = bpe * n_events;                                                                                           \
+        const TilePlan p = tile_plan(a, THV, TWV, gy, 1024);          /* two resident blocks per CU */                            \
+        const int tiles_w = p.tiles_w, tiles_h = p.tiles_h, tpe = p.tpe, tpb = p.tpb, bpe = p.bpe, nblk = p.nblk;                  \
         CONV_PLAN_POINT(bpe, 1)                                                                                                    \
         const size_t halo = (size_t)(THV + 2) * (TWV + 2) * CINV, epi = (size_t)NWV * EpiLds<NTV>::FLOATS * 4;                     \
         const size_t lds = (size_t)NTV * 16 * 9 * CINV + (halo > epi ? halo : epi);                                                \
@@ -707,25 +536,9 @@ static int lds_fp8_launch(const ConvArgs& a, hipStream_t st) {
 int conv3x3_lds_launch(const ConvArgs& a, hipStream_t st) {
     if (a.taps != 9 || (a.src.rs != 0 && a.src.rs != 1) || a.Kpad != 9 * a.Cin || (a.Cin != 64 && a.Cin != 128)) return 0;
     if (a.src.scale != nullptr && a.Cin > AFF_MAXC) return 0;
-    const bool aff = a.src.scale != nullptr, relu = a.src.relu != 0;
     if (a.flags & IEAGAN_CONV_FP8) {          // forward launches and dgrad launches (plain prologue + ReLU-mask / BatchNorm-backward epilogue)
-        int r = 0;
-        if (a.bnb_scale != nullptr) r = (a.src.rs == 0 && !aff && !relu) ? lds_fp8_launch<false, false, 0, true>(a, st) : 0;
-        else if (a.src.rs == 0) r = aff ? (relu ? lds_fp8_launch<true, true, 0>(a, st) : lds_fp8_launch<true, false, 0>(a, st))
-                                   : (relu ? lds_fp8_launch<false, true, 0>(a, st) : lds_fp8_launch<false, false, 0>(a, st));
-        else r = aff ? (relu ? lds_fp8_launch<true, true, 1>(a, st) : lds_fp8_launch<true, false, 1>(a, st))
-                     : (relu ? lds_fp8_launch<false, true, 1>(a, st) : lds_fp8_launch<false, false, 1>(a, st));
+        const int r = dispatch_prologue(a, [&](auto AFF, auto RELU, auto RS, auto BNB) { return lds_fp8_launch<AFF(), RELU(), RS(), BNB()>(a, st); });
         if (r != 0) return r;
     }
-    if (a.src.rs == 0) {
-        if (aff && relu) return lds_launch<true, true, 0, false>(a, st);
-        if (aff) return lds_launch<true, false, 0, false>(a, st);
-        if (relu) return lds_launch<false, true, 0, false>(a, st);
-        if (a.bnb_scale != nullptr) return lds_launch<false, false, 0, true>(a, st);
-        return lds_launch<false, false, 0, false>(a, st);
-    }
-    if (aff && relu) return lds_launch<true, true, 1, false>(a, st);
-    if (aff) return lds_launch<true, false, 1, false>(a, st);
-    if (relu) return lds_launch<false, true, 1, false>(a, st);
-    return lds_launch<false, false, 1, false>(a, st);
+    return dispatch_prologue(a, [&](auto AFF, auto RELU, auto RS, auto BNB) { return lds_launch<AFF(), RELU(), RS(), BNB()>(a, st); });
 }

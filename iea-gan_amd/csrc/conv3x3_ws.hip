@@ -10,7 +10,7 @@
 // consecutive tiles inside one statistics group, weights stay in LDS, the statistics are flushed once per block.
 #include "common.h"
 #include "conv_args.h"
-#include "conv_common.h"
+#include "conv3x3_tile.h"
 
 #define WS_H 8
 #define WS_W 32
@@ -41,15 +41,8 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 4 ? 4 : 3)) void conv3x3_ws
     const bool consumer = wave < NCW;
     const int lr = lane & 15, lg = lane >> 4;
     const int H = a.H, W = a.W;
-    int bid = blockIdx.x;
-    {   // XCD-aware order: each XCD (blocks b, b+8, ...) walks a contiguous run of tiles
-        const int q = nblk / 8, r = nblk % 8, xcd = bid % 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
-    const int event = bid / bpe;
-    const int t0 = event * tpe + (bid - event * bpe) * tpb;
-    const int t1 = min(t0 + tpb, (event + 1) * tpe);
-    const int ntl = t1 - t0;
+    const TileRun run = tile_run(nblk, 1, bpe, tpe, tpb);
+    const int t0 = run.t0, ntl = run.t1 - run.t0;
 
     // weights -> LDS once per block (all 8 waves)
     for (int idx = threadIdx.x; idx < NT * 16 * (KP / 8); idx += (NCW + 4) * 64) {
@@ -57,12 +50,7 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 4 ? 4 : 3)) void conv3x3_ws
         *(bf16x8*)(wlds + row * WSB + kc * 16) = *(const bf16x8*)((const bf16*)a.w + (long)row * KP + kc * 8);
     }
 
-    auto tile_coords = [&](int t, int& n, int& h0, int& w0) {
-        n = t / (tiles_w * tiles_h);
-        const int trem = t - n * tiles_w * tiles_h;
-        h0 = (trem / tiles_w) * WS_H;
-        w0 = (trem % tiles_w) * WS_W;
-    };
+    auto tile_coords = [&](int t, int& n, int& h0, int& w0) { tile_origin<WS_H, WS_W>(t, tiles_w, tiles_h, n, h0, w0); };
 
     // The two roles are separate loops (not one loop with a role branch inside): their register live ranges then do not overlap
     // and the kernel is allocated max(producer, consumer) registers instead of the sum.  Both execute the same barriers:
@@ -77,20 +65,7 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 4 ? 4 : 3)) void conv3x3_ws
         auto load_tile = [&](int t, bf16x8(&raw)[PF], unsigned& okmask) {
             int n, h0, w0;
             tile_coords(t, n, h0, w0);
-            okmask = 0;
-#pragma unroll
-            for (int j = 0; j < PF; ++j) {
-                // UNCONDITIONAL loads (coordinates clamped into the image, the padding ring zeroed by okmask in store_tile): under a
-                // per-lane condition the compiler cannot count the younger loads of the other register set and drains the counter
-                // -- vmcnt(0) -- before every store_tile, which left ONE tile in flight instead of two
-                const int idx = min(ptid + j * 256, TOT - 1);
-                const int hp = idx / CH, cc = idx - hp * CH;
-                const int hh = h0 - 1 + hp / AW, ww = w0 - 1 + hp % AW;
-                const int hc = min(max(hh, 0), H - 1), wc = min(max(ww, 0), W - 1);
-                const int sh_ = (RS == 1) ? (hc >> 1) : hc, sw_ = (RS == 1) ? (wc >> 1) : wc;
-                raw[j] = *(const bf16x8*)((const bf16*)a.src.x + (((long)n * a.src.Hs + sh_) * a.src.Ws + sw_) * a.src.Cx + cc * 8);
-                if (ptid + j * 256 < TOT && hh >= 0 && hh < H && ww >= 0 && ww < W) okmask |= 1u << j;
-            }
+            halo_request<RS, CH, AW, TOT, 256>(a.src, H, W, n, h0, w0, ptid, raw, okmask);      // (two register sets in flight)
         };
         auto store_tile = [&](int t, const bf16x8(&raw)[PF], unsigned okmask, char* dst) {
             int n, h0, w0;
@@ -109,23 +84,7 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 4 ? 4 : 3)) void conv3x3_ws
                 const int idx = ptid + j * 256;
                 if (idx >= TOT) continue;
                 const int hp = idx / CH, cc = idx - hp * CH;
-                bf16x8 o = zero8();
-                if (okmask & (1u << j)) {
-                    if (!AFF && RELU) {
-                        o = relu8(raw[j]);
-                    } else if (AFF) {
-                        const f32x8 sc = *(const f32x8*)(aff_w + cc * 8), sh = *(const f32x8*)(aff_w + 32 + cc * 8);
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            float v = bf2f(raw[j][i]) * sc[i] + sh[i];
-                            if (RELU) v = fmaxf(v, 0.f);
-                            o[i] = f2bf(v);
-                        }
-                    } else {
-                        o = raw[j];
-                    }
-                }
-                *(bf16x8*)(dst + hp * PS + cc * 16) = o;
+                *(bf16x8*)(dst + hp * PS + cc * 16) = prologue_chunk<AFF, RELU>(raw[j], okmask & (1u << j), aff_w + cc * 8, aff_w + 32 + cc * 8);
             }
         };
         // produce step r (runs next to the consumers' tile r): tile r+1 -> the other halo buffer, then request tile r+3 into the
@@ -251,14 +210,7 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 4 ? 4 : 3)) void conv3x3_ws
         }
 #pragma unroll
         for (int half = 0; half < RPW; ++half) {           // tile row RPW*wave + half: 32 pixels
-            const int hh = h0 + RPW * wave + half;
-            auto pix = [&](int row, long& m, int& nn, int& h, int& w) -> bool {
-                nn = n;
-                h = hh;
-                w = w0 + row;
-                m = ((long)n * H + h) * W + w;
-                return FULL ? true : (h < H && w < W);
-            };
+            const tile_pix<2, FULL> pix(n, h0, w0, 2 * (RPW * wave + half), H, W);
             const f32x4(&sub)[2][NT] = *reinterpret_cast<const f32x4(*)[2][NT]>(&acc[2 * half]);
             if (half == 0 && has_mask) mask_request(t0 + min(r + 1, ntl - 1), mk_nxt);      // (last tile: re-requests itself, unused)
             if (has_mask) conv_epilogue<BNB, NT>(a, sub, epi, 0, pix, s1, s2, bias_r, &mk_cur[half * EIT]);      // (two calls: a selected
@@ -270,21 +222,12 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 4 ? 4 : 3)) void conv3x3_ws
         }
         __syncthreads();
     }
-    if (a.stats != nullptr && ntl > 0) stats_flush<NT, NCW>(a, s1, s2, 0, red, epi_all, bid, event);
+    if (a.stats != nullptr && ntl > 0) stats_flush<NT, NCW>(a, s1, s2, 0, red, epi_all, run.bid, run.event);
 }
 
 template <bool AFF, bool RELU, int RS, bool BNB, bool MPF, bool FULL>
 static int ws_launch_f(const ConvArgs& a, hipStream_t st) {
-    const int tiles_w = (a.W + WS_W - 1) / WS_W, tiles_h = (a.H + WS_H - 1) / WS_H;
-    const int ntiles = a.N * tiles_w * tiles_h;
-    const int n_events = (a.stats != nullptr && a.n_per_event > 0) ? a.N / a.n_per_event : 1;
-    const int tpe = ntiles / n_events;
-    int bpe = (a.Cin == 16 ? 512 : 256) / n_events;      // persistent blocks: two (C = 16) / one (C = 32) per CU
-    if (bpe < 1) bpe = 1;
-    int tpb = (tpe + bpe - 1) / bpe;
-    if (tpb < 1) tpb = 1;
-    bpe = (tpe + tpb - 1) / tpb;
-    const int nblk = bpe * n_events;
+    const TilePlan p = tile_plan_events(a, WS_H, WS_W, a.Cin == 16 ? 512 : 256, 1);      // persistent blocks: two (C = 16) / one (C = 32) per CU
 #define WS_GO(CINV, NCWV)                                                                                                    \
     {                                                                                                                        \
         constexpr int NTV = CINV / 16;                                                                                       \
@@ -292,17 +235,10 @@ static int ws_launch_f(const ConvArgs& a, hipStream_t st) {
         size_t tail = (size_t)NCWV * EpiLds<NTV>::FLOATS * 4;                                                                \
         if (tail < (size_t)NCWV * STATS_SX_FLOATS * 4) tail = (size_t)NCWV * STATS_SX_FLOATS * 4;                             \
         const size_t lds = (size_t)NTV * 16 * (KPV * 2 + 16) + 2 * (size_t)(WS_H + 2) * (WS_W + 2) * (CINV * 2 + 16) + tail;  \
-        CONV_PLAN_POINT(bpe, 1)                                                                                              \
-        auto kern = conv3x3_ws_kernel<AFF, RELU, RS, CINV, BNB, MPF, NCWV, FULL>;                                            \
-        static bool attr_set = false;                                                                                        \
-        if (!attr_set) {                                                                                                     \
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-                ieagan_set_error("conv3x3_ws: cannot reserve %zu bytes of LDS", lds);                                        \
-                return IEAGAN_ELAUNCH;                                                                                       \
-            }                                                                                                                \
-            attr_set = true;                                                                                                 \
-        }                                                                                                                    \
-        hipLaunchKernelGGL(kern, dim3(nblk), dim3((NCWV + 4) * 64), lds, st, a, tiles_w, tiles_h, tpe, tpb, nblk, bpe);      \
+        CONV_PLAN_POINT(p.bpe, 1)                                                                                            \
+        constexpr auto kern = conv3x3_ws_kernel<AFF, RELU, RS, CINV, BNB, MPF, NCWV, FULL>;                                  \
+        if (reserve_lds<kern>(lds, "conv3x3_ws") != 0) return IEAGAN_ELAUNCH;                                                \
+        hipLaunchKernelGGL(kern, dim3(p.nblk), dim3((NCWV + 4) * 64), lds, st, a, p.tiles_w, p.tiles_h, p.tpe, p.tpb, p.nblk, p.bpe); \
     }
     // C = 16: 4 consumer + 4 producer waves, two blocks per CU
     WS_GO(16, 4)
@@ -316,19 +252,6 @@ static int ws_launch_c(const ConvArgs& a, hipStream_t st) {
     return ws_launch_f<AFF, RELU, RS, BNB, MPF, false>(a, st);
 }
 
-template <int RS>
-static int ws_launch_pro(const ConvArgs& a, hipStream_t st) {
-    const bool aff = a.src.scale != nullptr, relu = a.src.relu != 0;
-    if (aff && !relu) return 0;                                              // no layer of the path has an affine prologue without ReLU
-    if (a.mask != nullptr && (aff || relu)) return 0;                        // a masked epilogue belongs to a dgrad launch (plain prologue)
-    if (aff) return ws_launch_c<true, true, RS, false, false>(a, st);
-    if (relu) return ws_launch_c<false, true, RS, false, false>(a, st);
-    if (RS == 0 && a.bnb_scale != nullptr) return ws_launch_c<false, false, (RS == 0 ? 0 : RS), (RS == 0), (RS == 0)>(a, st);
-    if (RS == 0 && a.mask != nullptr) return ws_launch_c<false, false, (RS == 0 ? 0 : RS), false, (RS == 0)>(a, st);
-    if (a.mask != nullptr) return 0;
-    return ws_launch_c<false, false, RS, false, false>(a, st);
-}
-
 // 1 = launched, 0 = not applicable (the caller falls back to conv3x3_halo)
 int conv3x3_ws_launch(const ConvArgs& a, hipStream_t st) {
     // C = 32 needs 92-110 KB of LDS, i.e. one block per CU: measured slower than conv3x3_halo's three 4-wave blocks with 4 consumer
@@ -338,5 +261,14 @@ int conv3x3_ws_launch(const ConvArgs& a, hipStream_t st) {
     if (a.Kpad != ((9 * a.Cin + 31) / 32) * 32 || a.src.Cx % 8 != 0) return 0;
     const int tiles = a.N * ((a.W + WS_W - 1) / WS_W) * ((a.H + WS_H - 1) / WS_H);
     if (tiles < 1024) return 0;                   // < 2 tiles per persistent block: nothing to pipeline
-    return a.src.rs == 0 ? ws_launch_pro<0>(a, st) : ws_launch_pro<1>(a, st);
+    const bool aff = a.src.scale != nullptr, relu = a.src.relu != 0;
+    if (aff && !relu) return 0;            // no layer of the path has an affine prologue without ReLU
+    if (a.mask != nullptr) {               // a masked epilogue belongs to a dgrad launch: plain same-resolution prologue, mask chunks prefetched
+        if (aff || relu || a.src.rs != 0) return 0;
+        return a.bnb_scale != nullptr ? ws_launch_c<false, false, 0, true, true>(a, st) : ws_launch_c<false, false, 0, false, true>(a, st);
+    }
+    return dispatch_prologue(a, [&](auto AFF, auto RELU, auto RS, auto BNB) {
+        if constexpr (BNB() || (AFF() && !RELU())) return 0;      // (refused above / has its input as mask)
+        else return ws_launch_c<AFF(), RELU(), RS(), false, false>(a, st);
+    });
 }

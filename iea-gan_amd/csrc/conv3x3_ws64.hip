@@ -17,13 +17,10 @@
 // 4 KB of static rows = 155 KB, one persistent block per CU.
 #include "common.h"
 #include "conv_args.h"
-#include "conv_common.h"
+#include "conv3x3_tile.h"
 
 #define W64_H 8
 #define W64_W 16
-
-// same swizzle as conv3x3_lds.hip (rows of 8 or 72 chunks: CPR % 16 == 8)
-__device__ __forceinline__ int w64_swz(int r, int chunk) { return (chunk & ~7) | ((chunk ^ ((r >> 1) & 7)) & 7); }
 
 constexpr int W64_CIN = 64, W64_NT = 4, W64_NCW = 4;
 constexpr int W64_K = 9 * W64_CIN, W64_WCH = W64_K / 8, W64_CH = W64_CIN / 8;
@@ -55,30 +52,18 @@ __global__ __launch_bounds__(512, 1) void conv3x3_ws64_kernel(ConvArgs a, int ti
     const bool consumer = wave < NCW;
     const int lr = lane & 15, lg = lane >> 4;
     const int H = a.H, W = a.W;
-    int bid = blockIdx.x;
-    {   // XCD-aware order: each XCD (blocks b, b+8, ...) walks a contiguous run of tiles
-        const int q = nblk / 8, r = nblk % 8, xcd = bid % 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
-    const int event = bid / bpe;
-    const int t0 = event * tpe + (bid - event * bpe) * tpb;
-    const int t1 = min(t0 + tpb, (event + 1) * tpe);
-    const int ntl = t1 - t0;
+    const TileRun run = tile_run(nblk, 1, bpe, tpe, tpb);
+    const int t0 = run.t0, t1 = run.t1, ntl = t1 - t0;
     if (ntl <= 0) return;                                    // the whole block, before any barrier
 
     // weights -> LDS once per block (all 8 waves)
 #pragma unroll 3
     for (int idx = threadIdx.x; idx < NT * 16 * WCH; idx += 512) {
         const int row = idx / WCH, kc = idx - row * WCH;
-        *(bf16x8*)(wsm + (row * WCH + w64_swz(row, kc)) * 16) = *(const bf16x8*)((const bf16*)a.w + (long)row * a.Kpad + kc * 8);
+        *(bf16x8*)(wsm + swz_offset<WCH>(row, row, kc)) = *(const bf16x8*)((const bf16*)a.w + (long)row * a.Kpad + kc * 8);
     }
 
-    auto tile_coords = [&](int t, int& n, int& h0, int& w0) {
-        n = t / (tiles_w * tiles_h);
-        const int trem = t - n * tiles_w * tiles_h;
-        h0 = (trem / tiles_w) * W64_H;
-        w0 = (trem % tiles_w) * W64_W;
-    };
+    auto tile_coords = [&](int t, int& n, int& h0, int& w0) { tile_origin<W64_H, W64_W>(t, tiles_w, tiles_h, n, h0, w0); };
 
     // The two roles are separate loops: their register live ranges do not overlap and the kernel is allocated max(producer,
     // consumer) registers.  Both execute the same barriers: one after the preamble, two per tile, one for the statistics flush.
@@ -92,19 +77,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_ws64_kernel(ConvArgs a, int ti
         auto load_tile = [&](int t, bf16x8(&raw)[PF], unsigned& okmask) __attribute__((always_inline)) {
             int n, h0, w0;
             tile_coords(t, n, h0, w0);
-            okmask = 0;
-#pragma unroll
-            for (int j = 0; j < PF; ++j) {
-                // unconditional loads (coordinates clamped into the image, the padding ring zeroed by okmask in store_tile), so that
-                // the compiler can count the younger loads of the other register set instead of draining the counter
-                const int idx = min(ptid + j * 256, TOT - 1);
-                const int hp = idx / CH, cc = idx - hp * CH;
-                const int hh = h0 - 1 + hp / AW, ww = w0 - 1 + hp % AW;
-                const int hc = min(max(hh, 0), H - 1), wc = min(max(ww, 0), W - 1);
-                const int sh_ = (RS == 1) ? (hc >> 1) : hc, sw_ = (RS == 1) ? (wc >> 1) : wc;
-                raw[j] = *(const bf16x8*)((const bf16*)a.src.x + (((long)n * a.src.Hs + sh_) * a.src.Ws + sw_) * a.src.Cx + cc * 8);
-                if (ptid + j * 256 < TOT && hh >= 0 && hh < H && ww >= 0 && ww < W) okmask |= 1u << j;
-            }
+            halo_request<RS, CH, AW, TOT, 256>(a.src, H, W, n, h0, w0, ptid, raw, okmask);
         };
         auto store_tile = [&](int t, const bf16x8(&raw)[PF], unsigned okmask, char* dst) __attribute__((always_inline)) {
             int n, h0, w0;
@@ -123,24 +96,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_ws64_kernel(ConvArgs a, int ti
                 const int idx = ptid + j * 256;
                 if (idx >= TOT) continue;
                 const int hp = idx / CH, cc = idx - hp * CH;
-                bf16x8 o = zero8();
-                if (okmask & (1u << j)) {
-                    if (!AFF && RELU) {
-                        o = relu8(raw[j]);
-                    } else if (AFF) {
-                        const f32x8 sc = *(const f32x8*)(aff_w + cc * 8), sh = *(const f32x8*)(aff_w + CIN + cc * 8);
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            float v = bf2f(raw[j][i]);
-                            v = v * sc[i] + sh[i];
-                            if (RELU) v = fmaxf(v, 0.f);
-                            o[i] = f2bf(v);
-                        }
-                    } else {
-                        o = raw[j];
-                    }
-                }
-                *(bf16x8*)(dst + (hp * CH + w64_swz(hp % AW, cc)) * 16) = o;
+                *(bf16x8*)(dst + swz_offset<CH>(hp, hp % AW, cc)) = prologue_chunk<AFF, RELU>(raw[j], okmask & (1u << j), aff_w + cc * 8, aff_w + CIN + cc * 8);
             }
         };
         // ---- the epilogue of tile r-1 runs HERE, next to the consumers' K loop of tile r: the consumers only put their accumulators
@@ -190,13 +146,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_ws64_kernel(ConvArgs a, int ti
                 __builtin_amdgcn_wave_barrier();
                 bnb_n = n;
             }
-            auto pix = [&](int row, long& m, int& nn, int& h, int& w) -> bool {      // one m-tile of each of consumer wl's two tile rows
-                nn = n;
-                h = h0 + 2 * wl + (row >> 4);
-                w = w0 + (row & 15);
-                m = ((long)n * H + h) * W + w;
-                return FULL ? true : (h < H && w < W);
-            };
+            const tile_pix<1, FULL> pix(n, h0, w0, 2 * wl, H, W);       // one m-tile of each of consumer wl's two tile rows
             if constexpr (BNB) conv_epilogue_finish<true, NT>(ae, epi, 0, pix, s1, s2, bias_r, mk_cur, aff_w);
             else if constexpr (MPF) conv_epilogue_finish<false, NT>(ae, epi, 0, pix, s1, s2, bias_r, mk_cur);
             else conv_epilogue_finish<false, NT>(ae, epi, 0, pix, s1, s2, bias_r, nullptr);
@@ -240,93 +190,34 @@ __global__ __launch_bounds__(512, 1) void conv3x3_ws64_kernel(ConvArgs a, int ti
     }
 
     // ------------------------------------------------------------------------------------------ consumers
-    // Fragment addresses = per-lane register (swizzled chunk offset) + immediate (tap / k-step / n-tile displacement):
-    //   A: pixel (row 2*wave + m + dy, col lr + dx) of the halo, chunk cq*4 + lg of its 8 chunks
-    //   B: weight row nt*16 + lr, chunk ks*4 + lg
-    constexpr int NV = CH / 4;
-    int offA[2][3][NV];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const int base = ((2 * wave + m) * AW + lr) * CH * 16;
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-            for (int v = 0; v < NV; ++v) offA[m][dx][v] = base + w64_swz(lr + dx, v * 4 + lg) * 16;
-    }
-    int offB[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) offB[v] = lr * WCH * 16 + w64_swz(lr, v * 4 + lg) * 16;
+    // the per-wave register tile, fragment mapping and K loop of conv3x3_lds: two m-tiles (tile rows 2*wave, 2*wave + 1) x 4 n-tiles
+    int offA[2][3][CIN / 32], offB[CIN / 32];
+    lds_frag_offsets<CIN, 2, 1, AW>(2 * wave, lr, lg, offA, offB);
     float* epi = epi_all + wave * EpiLds<NT>::FLOATS;
     __syncthreads();
     for (int r = 0; r < ntl; ++r) {
         const char* hsm = halo0 + (r & 1) * HALO_BYTES;
         f32x4 acc[2][NT];
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[m][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        auto lda = [&](int ks, bf16x8(&x)[2]) {
-            const int tap = (ks * 32) / CIN, cq = ((ks * 32) % CIN) / 32;
-            const int imm = ((tap / 3) * AW + (tap % 3)) * CH * 16;
-#pragma unroll
-            for (int m = 0; m < 2; ++m) x[m] = *(const bf16x8*)(hsm + offA[m][tap % 3][cq] + imm);
-        };
-        auto ldb = [&](int ks, bf16x8(&b)[NT]) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) b[nt] = *(const bf16x8*)(wsm + offB[ks % NV] + nt * 16 * WCH * 16 + (ks / NV) * NV * 64);
-        };
-        // one-step-ahead software pipeline over the K steps (order of conv3x3_lds: bit-identical accumulation)
-        bf16x8 aq[2][2], bq[2][NT];
-        lda(0, aq[0]);
-        ldb(0, bq[0]);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            if (ks + 1 < KS) {
-                lda(ks + 1, aq[(ks + 1) & 1]);
-                ldb(ks + 1, bq[(ks + 1) & 1]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ks & 1][m], bq[ks & 1][nt], acc[m][nt], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        kloop_swizzled<CIN, NT, 2, AW>(hsm, wsm, offA, offB, acc);
         __syncthreads();                  // the data-movement waves have finished tile r-1: the transpose buffers are free
         conv_epilogue_put<NT>(acc, epi);
         __syncthreads();                  // tile r handed over; the halo of tile r+1 is in place
     }
     if (a.stats != nullptr) {
         __syncthreads();                  // the partials of the data-movement waves are folded into red[]
-        stats_add<NT, NCW>(a, 0, red, bid, event);
+        stats_add<NT, NCW>(a, 0, red, run.bid, run.event);
     }
 }
 
 template <bool AFF, bool RELU, int RS, bool BNB, bool MPF, bool FULL>
 static int ws64_launch_f(const ConvArgs& a, hipStream_t st) {
-    const int tiles_w = (a.W + W64_W - 1) / W64_W, tiles_h = (a.H + W64_H - 1) / W64_H;
-    const int ntiles = a.N * tiles_w * tiles_h;
-    const int n_events = (a.stats != nullptr && a.n_per_event > 0) ? a.N / a.n_per_event : 1;
-    const int tpe = ntiles / n_events;
-    int bpe = 256 / n_events;                             // one persistent block per CU; a block's tiles stay inside one event
-    if (bpe < 1) bpe = 1;
-    int tpb = (tpe + bpe - 1) / bpe;
-    if (tpb < 4) tpb = 4;                                 // a block stages 73.7 KB of weights, as much as three halos: at least 4 tiles for them
-    if (tpb > tpe) tpb = tpe;
-    bpe = (tpe + tpb - 1) / tpb;
-    const int nblk = bpe * n_events;
-    CONV_PLAN_POINT(bpe, 1)
-    auto kern = conv3x3_ws64_kernel<AFF, RELU, RS, BNB, MPF, FULL>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, W64_LDS_BYTES) != hipSuccess) {
-            ieagan_set_error("conv3x3_ws64: cannot reserve %d bytes of LDS", W64_LDS_BYTES);
-            return IEAGAN_ELAUNCH;
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), (size_t)W64_LDS_BYTES, st, a, tiles_w, tiles_h, tpe, tpb, nblk, bpe);
+    // one persistent block per CU; a block's tiles stay inside one event.  A block stages 73.7 KB of weights, as much as three halos:
+    // at least 4 tiles for them
+    const TilePlan p = tile_plan_events(a, W64_H, W64_W, 256, 4);
+    CONV_PLAN_POINT(p.bpe, 1)
+    constexpr auto kern = conv3x3_ws64_kernel<AFF, RELU, RS, BNB, MPF, FULL>;
+    if (reserve_lds<kern>(W64_LDS_BYTES, "conv3x3_ws64") != 0) return IEAGAN_ELAUNCH;
+    hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(512), (size_t)W64_LDS_BYTES, st, a, p.tiles_w, p.tiles_h, p.tpe, p.tpb, p.nblk, p.bpe);
     return 1;
 }
 
@@ -334,18 +225,6 @@ template <bool AFF, bool RELU, int RS, bool BNB, bool MPF>
 static int ws64_launch_c(const ConvArgs& a, hipStream_t st) {
     if (a.H % W64_H == 0 && a.W % W64_W == 0) return ws64_launch_f<AFF, RELU, RS, BNB, MPF, true>(a, st);
     return ws64_launch_f<AFF, RELU, RS, BNB, MPF, false>(a, st);
-}
-
-template <int RS>
-static int ws64_launch_pro(const ConvArgs& a, hipStream_t st) {
-    const bool aff = a.src.scale != nullptr, relu = a.src.relu != 0;
-    if (a.mask != nullptr && (aff || relu || RS != 0)) return 0;            // a masked epilogue belongs to a dgrad launch (plain prologue)
-    if (aff && relu) return ws64_launch_c<true, true, RS, false, false>(a, st);
-    if (aff) return ws64_launch_c<true, false, RS, false, false>(a, st);
-    if (relu) return ws64_launch_c<false, true, RS, false, false>(a, st);
-    if (RS == 0 && a.bnb_scale != nullptr) return ws64_launch_c<false, false, 0, (RS == 0), (RS == 0)>(a, st);
-    if (RS == 0 && a.mask != nullptr) return ws64_launch_c<false, false, 0, false, (RS == 0)>(a, st);
-    return ws64_launch_c<false, false, RS, false, false>(a, st);
 }
 
 // Tiles (8x16 pixels) from which a launch goes to this kernel, chosen by same-box alternation against conv3x3_lds at N = 40 (DESIGN
@@ -366,5 +245,12 @@ int conv3x3_ws64_launch(const ConvArgs& a, hipStream_t st) {
     if (a.H < W64_H || a.W < W64_W || a.ra != nullptr || a.rb != nullptr) return 0;
     const long tiles = (long)a.N * ((a.W + W64_W - 1) / W64_W) * ((a.H + W64_H - 1) / W64_H);
     if (tiles < (a.src.scale != nullptr ? W64_MIN_TILES_AFF : W64_MIN_TILES) && !(a.flags & IEAGAN_CONV_FORCE_WS64)) return 0;
-    return a.src.rs == 0 ? ws64_launch_pro<0>(a, st) : ws64_launch_pro<1>(a, st);
+    if (a.mask != nullptr) {               // a masked epilogue belongs to a dgrad launch: plain same-resolution prologue, mask chunks prefetched
+        if (a.src.scale != nullptr || a.src.relu != 0 || a.src.rs != 0) return 0;
+        return a.bnb_scale != nullptr ? ws64_launch_c<false, false, 0, true, true>(a, st) : ws64_launch_c<false, false, 0, false, true>(a, st);
+    }
+    return dispatch_prologue(a, [&](auto AFF, auto RELU, auto RS, auto BNB) {
+        if constexpr (BNB()) return 0;     // (the BatchNorm-backward epilogue has its input as mask: taken above)
+        else return ws64_launch_c<AFF(), RELU(), RS(), false, false>(a, st);
+    });
 }

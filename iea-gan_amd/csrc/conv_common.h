@@ -1,4 +1,5 @@
-// Device helpers shared by the convolution kernels (conv_igemm.hip, conv1x1_stream.hip).
+// Device helpers shared by all convolution kernels (1x1 and 3x3, forward and backward files): the fused prologue of 8 channels, the
+// shared epilogue and the statistics flush.  What only the 3x3 tile kernels share lives in conv3x3_tile.h.
 #pragma once
 #include "common.h"
 #include "conv_args.h"
@@ -14,16 +15,17 @@ __device__ __forceinline__ void stage_aff(float* aff, const SrcDesc& s, int n, i
     }
 }
 
+// 8 floats of an LDS table through an LDS-QUALIFIED pointer.  As a generic pointer these are FLAT loads, which count on the
+// vector-memory counter as well -- every use then waits for ALL outstanding global prefetches.
+__device__ __forceinline__ f32x8 lds_load8(const float* p) { return *(const __attribute__((address_space(3))) f32x8*)p; }
+
 template <bool AFF, bool RELU>
 __device__ __forceinline__ void xform8(float (&v)[8], const SrcDesc& s, int n, int c, const float* aff = nullptr) {
     if (AFF) {
         f32x8 sc, sh;
         if (aff != nullptr) {
-            // `aff` is an LDS table: read it through an LDS-qualified pointer.  As a generic pointer these were FLAT loads, which
-            // count on the vector-memory counter as well -- every use then waited for ALL outstanding global prefetches.
-            typedef const __attribute__((address_space(3))) f32x8* lds_f32x8;
-            sc = *(lds_f32x8)(aff + c);
-            sh = *(lds_f32x8)(aff + AFF_MAXC + c);
+            sc = lds_load8(aff + c);
+            sh = lds_load8(aff + AFF_MAXC + c);
         } else {
             sc = *(const f32x8*)(s.scale + (long)n * s.aff_nstride + c);
             sh = *(const f32x8*)(s.shift + (long)n * s.aff_nstride + c);
@@ -222,7 +224,7 @@ __device__ __forceinline__ void conv_epilogue_finish(const ConvArgs& a, const fl
             pix(row, mm, n, h, w);
             const long so = (long)n * a.bnb_nstride + co0;
             f32x4 sc0, sc1, sh0, sh1;
-            if (bnb_pre != nullptr) {           // LDS-qualified reads (as a generic pointer they would be FLAT loads, see xform8)
+            if (bnb_pre != nullptr) {           // LDS-qualified reads (as a generic pointer they would be FLAT loads, see lds_load8)
                 typedef const __attribute__((address_space(3))) f32x4* lds_f32x4;
                 sc0 = *(lds_f32x4)(bnb_pre + cc * 8), sc1 = *(lds_f32x4)(bnb_pre + cc * 8 + 4);
                 sh0 = *(lds_f32x4)(bnb_pre + NT * 16 + cc * 8), sh1 = *(lds_f32x4)(bnb_pre + NT * 16 + cc * 8 + 4);

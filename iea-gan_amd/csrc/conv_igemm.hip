@@ -14,7 +14,7 @@
 // D[row 4*(l>>4)+r][col l&15].
 #include "common.h"
 #include "conv_args.h"
-#include "conv_common.h"
+#include "conv3x3_tile.h"
 #include <stdio.h>
 
 // ------------------------------------------------------------------------------------------------
@@ -185,12 +185,7 @@ static int launch_gather_nt(const ConvArgs& a0, hipStream_t st) {
 
 template <int TAPS, int RS>
 static int launch_gather_pro(const ConvArgs& a, hipStream_t st) {
-    const bool aff = a.src.scale != nullptr, relu = a.src.relu != 0;
-    if (aff && relu) return launch_gather_nt<TAPS, true, true, RS>(a, st);
-    if (aff) return launch_gather_nt<TAPS, true, false, RS>(a, st);
-    if (relu) return launch_gather_nt<TAPS, false, true, RS>(a, st);
-    if (RS == 0 && a.bnb_scale != nullptr) return launch_gather_nt<TAPS, false, false, (RS == 0 ? 0 : RS), (RS == 0)>(a, st);   // BatchNorm-backward epilogue
-    return launch_gather_nt<TAPS, false, false, RS>(a, st);
+    return dispatch_prologue_rs<RS>(a, [&](auto AFF, auto RELU, auto, auto BNB) { return launch_gather_nt<TAPS, AFF(), RELU(), RS, BNB()>(a, st); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -224,18 +219,8 @@ __global__ __launch_bounds__(256, ((CIN >= 64 && PF == 0) ? 2 : (CIN == 16 ? 4 :
     const int chunks = Cin >> 3;
     const int total = AH * AW * chunks;
     char* smem = smem_all + (PF > 0 ? NT * 16 * WS : 0);   // halo (and, after the MFMA loop, epilogue) region
-    // XCD-aware order: blocks b and b+8 share an XCD (and its L2), so give each XCD a contiguous run of
-    // tiles -- neighbouring tiles then share their halo rows / weights through one L2.
-    int bid = blockIdx.x;
-    {
-        const int q = nblk / 8, r = nblk % 8, xcd = bid % 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
-    // a block stays inside ONE event (tpe tiles, bpe blocks per event): its statistics go to that event's accumulators with a
-    // single flush at the end (a flush inside the tile loop costs the C = 16 / 32 variants 40-60 spilled VGPRs)
-    const int event = bid / bpe;
-    const int t0 = event * tpe + (bid - event * bpe) * tpb;
-    const int t1 = min(t0 + tpb, (event + 1) * tpe);
+    const TileRun run = tile_run(nblk, 1, bpe, tpe, tpb);
+    const int t0 = run.t0, t1 = run.t1;
     const bool col_ok = (n_base + (NT - 1) * 16 + lr) < a.Cout;
 
     if (PF > 0) {   // weights -> LDS once per block: compile-time trip count (Kpad = 9 * CIN rounded up to 32), all loads of a batch first
@@ -263,12 +248,7 @@ __global__ __launch_bounds__(256, ((CIN >= 64 && PF == 0) ? 2 : (CIN == 16 ? 4 :
     int aff_n = -1;
     bf16x8 raw[PF > 0 ? PF : 1];
     unsigned okmask = 0;
-    auto tile_coords = [&](int t, int& n, int& h0, int& w0) {
-        n = t / (tiles_w * tiles_h);
-        const int trem = t - n * tiles_w * tiles_h;
-        h0 = (trem / tiles_w) * HT_H;
-        w0 = (trem % tiles_w) * HT_W;
-    };
+    auto tile_coords = [&](int t, int& n, int& h0, int& w0) { tile_origin<HT_H, HT_W>(t, tiles_w, tiles_h, n, h0, w0); };
     auto load_tile = [&](int t) {      // raw 16-byte loads of the halo of tile t (no transform yet)
         int n, h0, w0;
         tile_coords(t, n, h0, w0);
@@ -278,38 +258,19 @@ __global__ __launch_bounds__(256, ((CIN >= 64 && PF == 0) ? 2 : (CIN == 16 ? 4 :
             const int idx = threadIdx.x + j * 256;
             const int hp = idx / chunks, cc = idx - hp * chunks;
             const int hh = h0 - 1 + hp / AW, ww = w0 - 1 + hp % AW;
-            const bool ok = idx < total && hh >= 0 && hh < H && ww >= 0 && ww < W;
-            if (ok) {
-                const int sh_ = (RS == 1) ? (hh >> 1) : hh, sw_ = (RS == 1) ? (ww >> 1) : ww;
-                raw[j] = *(const bf16x8*)((const bf16*)a.src.x + (((long)n * a.src.Hs + sh_) * a.src.Ws + sw_) * a.src.Cx + cc * 8);
+            if (idx < total && hh >= 0 && hh < H && ww >= 0 && ww < W) {
+                raw[j] = *halo_src_chunk<RS>(a.src, n, hh, ww, cc);
                 okmask |= 1u << j;
             }
         }
     };
-    auto store_tile = [&](int t) {     // prologue transform + LDS write of the prefetched halo
-        int n, h0, w0;
-        tile_coords(t, n, h0, w0);
+    auto store_tile = [&]() {          // prologue transform + LDS write of the prefetched halo
 #pragma unroll
         for (int j = 0; j < PF; ++j) {
             const int idx = threadIdx.x + j * 256;
             if (idx >= total) continue;
             const int hp = idx / chunks, cc = idx - hp * chunks;
-            bf16x8 o = zero8();
-            if (okmask & (1u << j)) {
-                if (!AFF && RELU) {
-                    o = relu8(raw[j]);
-                } else if (AFF || RELU) {
-                    float v[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] = bf2f(raw[j][i]);
-                    xform8<AFF, RELU>(v, a.src, n, cc * 8, affp);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) o[i] = f2bf(v[i]);
-                } else {
-                    o = raw[j];
-                }
-            }
-            *(bf16x8*)(smem + hp * PS + cc * 16) = o;
+            *(bf16x8*)(smem + hp * PS + cc * 16) = prologue_chunk<AFF, RELU>(raw[j], okmask & (1u << j), aff_s + cc * 8, aff_s + AFF_MAXC + cc * 8);
         }
     };
 
@@ -334,7 +295,7 @@ __global__ __launch_bounds__(256, ((CIN >= 64 && PF == 0) ? 2 : (CIN == 16 ? 4 :
             __syncthreads();
         }
         if (PF > 0) {
-            store_tile(t);
+            store_tile();
         } else if constexpr (CIN >= 32) {
             // known channel count: the halo is fetched in batches of SB independent 16-byte loads per thread (all in flight
             // together), then transformed and written to LDS -- not one load -> wait -> store round trip per chunk
@@ -350,8 +311,7 @@ __global__ __launch_bounds__(256, ((CIN >= 64 && PF == 0) ? 2 : (CIN == 16 ? 4 :
                     const int hp = idx / CH, cc = idx - hp * CH;
                     const int hh = h0 - 1 + hp / AW, ww = w0 - 1 + hp % AW;
                     if (hh >= 0 && hh < H && ww >= 0 && ww < W) {
-                        const int sh_ = (RS == 1) ? (hh >> 1) : hh, sw_ = (RS == 1) ? (ww >> 1) : ww;
-                        rawb[j] = *(const bf16x8*)((const bf16*)a.src.x + (((long)n * a.src.Hs + sh_) * a.src.Ws + sw_) * a.src.Cx + cc * 8);
+                        rawb[j] = *halo_src_chunk<RS>(a.src, n, hh, ww, cc);
                         okb |= 1u << j;
                     }
                 }
@@ -360,22 +320,7 @@ __global__ __launch_bounds__(256, ((CIN >= 64 && PF == 0) ? 2 : (CIN == 16 ? 4 :
                     const int idx = threadIdx.x + (b0 + j) * 256;
                     if (b0 + j >= ITERS || idx >= TOT) continue;
                     const int hp = idx / CH, cc = idx - hp * CH;
-                    bf16x8 o = zero8();
-                    if (okb & (1u << j)) {
-                        if (!AFF && RELU) {
-                            o = relu8(rawb[j]);
-                        } else if (AFF || RELU) {
-                            float v[8];
-#pragma unroll
-                            for (int i = 0; i < 8; ++i) v[i] = bf2f(rawb[j][i]);
-                            xform8<AFF, RELU>(v, a.src, n, cc * 8, affp);
-#pragma unroll
-                            for (int i = 0; i < 8; ++i) o[i] = f2bf(v[i]);
-                        } else {
-                            o = rawb[j];
-                        }
-                    }
-                    *(bf16x8*)(smem + hp * PS + cc * 16) = o;
+                    *(bf16x8*)(smem + hp * PS + cc * 16) = prologue_chunk<AFF, RELU>(rawb[j], okb & (1u << j), aff_s + cc * 8, aff_s + AFF_MAXC + cc * 8);
                 }
             }
         } else {
@@ -459,58 +404,39 @@ __global__ __launch_bounds__(256, ((CIN >= 64 && PF == 0) ? 2 : (CIN == 16 ? 4 :
                         acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ks & 1][mt], bq[ks & 1][nt], acc[mt][nt], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
-        } else if constexpr (CIN >= 32) {      // channel count known at compile time (C = 16 measured faster as a rolled loop): straight-line K loop, every offset an immediate
-#pragma unroll
-            for (int ks = 0; ks < (9 * CIN + 31) / 32; ++ks) kstep(ks);
-        } else {
+        } else {                               // (C = 16 measured faster as a rolled loop than straight-line)
             for (int ks = 0; ks < ksteps; ++ks) kstep(ks);
         }
         __syncthreads();                                   // halo consumed: its LDS becomes the epilogue buffer
         float* epi = (float*)smem + wave * EpiLds<NT>::FLOATS;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {             // tile row 2*wave + half: 32 pixels
-            const int hh = h0 + 2 * wave + half;
-            auto pix = [&](int row, long& m, int& nn, int& h, int& w) -> bool {
-                nn = n;
-                h = hh;
-                w = w0 + row;
-                m = ((long)n * H + h) * W + w;
-                return h < H && w < W;
-            };
+            const tile_pix<2, false> pix(n, h0, w0, 2 * (2 * wave + half), H, W);
             const f32x4(&sub)[2][NT] = *reinterpret_cast<const f32x4(*)[2][NT]>(&acc[2 * half]);
             conv_epilogue<BNB, NT, 2, false>(a, sub, epi, n_base, pix, s1, s2);
         }
         __syncthreads();      // every wave has left its epilogue buffer: the region is the next tile's halo / the fold scratch
     }
-    if (a.stats != nullptr && t0 < t1) stats_flush<NT>(a, s1, s2, n_base, red, (float*)smem, bid, event);
+    if (a.stats != nullptr && t0 < t1) stats_flush<NT>(a, s1, s2, n_base, red, (float*)smem, run.bid, run.event);
 }
 
 template <bool AFF, bool RELU, int RS, bool BNB = false>
 static int launch_halo_nt(const ConvArgs& a, hipStream_t st) {
-    const int tiles_w = (a.W + HT_W - 1) / HT_W, tiles_h = (a.H + HT_H - 1) / HT_H;
-    const int ntiles = a.N * tiles_w * tiles_h;
-    // statistics groups: events of n_per_event images (forward: per-event BatchNorm statistics; BatchNorm-backward epilogue: every
-    // image its own group); without statistics the whole batch is one group
-    const int n_events = (a.stats != nullptr && a.n_per_event > 0) ? a.N / a.n_per_event : 1;
-    const int tpe = ntiles / n_events;
+    const TilePlan g = tile_grid(a, HT_H, HT_W);
+    const int ntiles = g.ntiles;
+    const int tpb = ntiles / 2048 > 8 ? 8 : ntiles / 2048;       // prefetching variants: 1 .. 8 tiles per block
     const size_t halo = (size_t)(HT_H + 2) * (HT_W + 2) * (a.Cin * 2 + 16);
-    int tpb = ntiles / 2048;
-    if (tpb < 1) tpb = 1;
-    if (tpb > 8) tpb = 8;
 #define HALO_LAUNCH(NTV, PFV, CINV)                                                                              \
     {                                                                                                        \
         size_t lds = halo;                                                                                   \
         const size_t epi = (size_t)4 * EpiLds<NTV>::FLOATS * 4;                                              \
         if (epi > lds) lds = epi;                                                                            \
         if (lds < 4 * STATS_SX_FLOATS * 4) lds = 4 * STATS_SX_FLOATS * 4;                                    \
-        int tp = (PFV) > 0 ? tpb : 1;                                                                        \
-        if ((PFV) > 0 && (CINV) >= 64) { tp = (ntiles + 255) / 256; if (tp > 8) tp = 8; }   /* one persistent block per CU */ \
         if ((PFV) > 0) lds += (size_t)NTV * 16 * (a.Kpad * 2 + 16);                                          \
-        const int bpe = (tpe + tp - 1) / tp;                                                                 \
-        const int nblk = bpe * n_events;                                                                     \
-        CONV_PLAN_POINT(bpe, 0)                                                                              \
-        hipLaunchKernelGGL((conv3x3_halo_kernel<AFF, RELU, RS, NTV, PFV, CINV, BNB>), dim3(nblk, (a.Cout + 16 * NTV - 1) / (16 * NTV)), \
-                           dim3(256), lds, st, a, tiles_w, tiles_h, tpe, tp, nblk, bpe);                     \
+        const TilePlan p = tile_split(g, (PFV) > 0 ? tpb : 1);                                               \
+        CONV_PLAN_POINT(p.bpe, 0)                                                                            \
+        hipLaunchKernelGGL((conv3x3_halo_kernel<AFF, RELU, RS, NTV, PFV, CINV, BNB>), dim3(p.nblk, (a.Cout + 16 * NTV - 1) / (16 * NTV)), \
+                           dim3(256), lds, st, a, p.tiles_w, p.tiles_h, p.tpe, p.tpb, p.nblk, p.bpe);        \
     }
     // prefetching variants: Cin = Cout = 16 / 32 (PF = ceil(340 * Cin/8 / 256) = 3 / 6)
     // small feature maps: fewer channels per block so that the grid still covers the 256 CUs
@@ -523,11 +449,8 @@ static int launch_halo_nt(const ConvArgs& a, hipStream_t st) {
     }
     else if (a.Cin == 16 && a.Cout == 16) HALO_LAUNCH(1, 3, 16)
     else if (a.Cin == 32 && a.Cout == 32) HALO_LAUNCH(2, 6, 32)
-    // (C = 64 with LDS-resident weights + prefetch was measured SLOWER -- 195-245 vs 270-320 TFLOP/s: one block of
-    //  4 waves per CU leaves the ds_read -> MFMA latency exposed; it needs a hand-pipelined K loop first.)
-    // C = 64 on large maps: weights resident in LDS (one persistent block per CU, next halo prefetched into registers):
-    // 478 vs 343 TFLOP/s at 64x192 -- the per-wave 16-byte weight fetches through L1 were the limiter
-    else if (a.Cin == 64 && a.Cout == 64 && ntiles >= 1024) HALO_LAUNCH(4, 11, 64)
+    // (C = 64 / 128 come here only past conv3x3_lds -- IEAGAN_CONV_NO_LDS_WEIGHTS, residual-free reference of the tests -- or on maps
+    //  that kernel does not take: weights from global / L1, one tile per block)
     else if (a.Cin == 64 && a.Cout % 64 == 0 && !small) HALO_LAUNCH(4, 0, 64)
     else if (a.Cin == 128 && a.Cout % 64 == 0 && !small) HALO_LAUNCH(4, 0, 128)
     else if (a.Cin == 128 && a.Cout % 32 == 0 && !(small && ntiles * (a.Cout / 32) < 512)) HALO_LAUNCH(2, 0, 128)
@@ -537,16 +460,6 @@ static int launch_halo_nt(const ConvArgs& a, hipStream_t st) {
     else HALO_LAUNCH(1, 0, 0)
 #undef HALO_LAUNCH
     return 0;
-}
-
-template <int RS>
-static int launch_halo_pro(const ConvArgs& a, hipStream_t st) {
-    const bool aff = a.src.scale != nullptr, relu = a.src.relu != 0;
-    if (aff && relu) return launch_halo_nt<true, true, RS>(a, st);
-    if (aff) return launch_halo_nt<true, false, RS>(a, st);
-    if (relu) return launch_halo_nt<false, true, RS>(a, st);
-    if (RS == 0 && a.bnb_scale != nullptr) return launch_halo_nt<false, false, (RS == 0 ? 0 : RS), (RS == 0)>(a, st);             // BatchNorm-backward epilogue
-    return launch_halo_nt<false, false, RS>(a, st);
 }
 
 int conv_gather_launch(const ConvArgs& a, hipStream_t st) {
@@ -594,7 +507,7 @@ int conv_gather_launch(const ConvArgs& a, hipStream_t st) {
         // C = 16 / 32 on large maps: wave-specialised producer / consumer kernel (conv3x3_ws.hip)
         if (rc == 0 && !(a.flags & IEAGAN_CONV_NO_LDS_WEIGHTS)) rc = conv3x3_ws_launch(a, st);
         if (rc < 0) return rc;
-        if (rc == 0) rc = (a.src.rs == 0) ? launch_halo_pro<0>(a, st) : launch_halo_pro<1>(a, st);
+        if (rc == 0) rc = dispatch_prologue(a, [&](auto AFF, auto RELU, auto RS, auto BNB) { return launch_halo_nt<AFF(), RELU(), RS(), BNB()>(a, st); });
         else rc = 0;
     } else if (a.taps == 9) {
         if (a.src.rs == 0) rc = launch_gather_pro<9, 0>(a, st);

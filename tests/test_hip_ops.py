@@ -152,7 +152,7 @@ def test_halo_and_gather_kernels_agree(dev):
     close(outs[0][1], outs[1][1], 1e-3, "halo vs gather stats")
 
 
-@pytest.mark.parametrize("N,Hh,Ww,C", [(40, 64, 192, 64),      # C = 64: conv3x3_lds (8 waves, 16x32 tiles) / halo kernel with LDS weights
+@pytest.mark.parametrize("N,Hh,Ww,C", [(40, 64, 192, 64),      # C = 64: conv3x3_ws64 (8x16 tiles) / halo kernel, weights from L1
                                        (6, 32, 96, 64),        # C = 64 on a small map
                                        (5, 20, 40, 64),        # C = 64, ragged tiles (20 % 16, 40 % 32)
                                        (4, 16, 48, 128),       # C = 128: conv3x3_lds (4 waves, 8x16 tiles)
@@ -190,6 +190,76 @@ def test_specialised_halo_variants_agree_with_gather(dev, N, Hh, Ww, C):
         close(outs[0][1], outs[1][1], 2e-3, tag + "lds / ws / halo vs gather stats")
         close(outs[2][0], outs[1][0], 4e-3, tag + "halo vs gather out")
         close(outs[2][1], outs[1][1], 2e-3, tag + "halo vs gather stats")
+
+
+# name: (C, N, H, W, flags that select the first family, events, (H, W) of the BatchNorm-backward variant).  The second family is always
+# conv3x3_halo (CONV_NO_LDS_WEIGHTS).  The launcher accepts per-group statistics only for groups of a whole number of 128-pixel blocks
+# (n_per_event * H * W % 128 == 0, whatever kernel takes the launch): the two events of the ws pair need H * W % 32 == 0, hence 124x248,
+# and the per-image accumulators of a BatchNorm-backward dgrad need H * W % 128 == 0, hence a shape of its own per pair (same tile counts
+# per image, still ragged in one direction).
+TILE_PAIRS = {
+    "lds_8wave_c64": (64, 25, 20, 40, "CONV_NO_WS64", 1, (24, 48)),     # 100 tile pairs: the least that selects the 8-wave form; ragged both ways
+    "lds_4wave_c64": (64, 2, 12, 40, "CONV_NO_WS64", 1, (24, 48)),
+    "lds_c128": (128, 2, 12, 24, None, 1, (12, 32)),
+    "ws_c16": (16, 8, 124, 248, None, 2, (124, 256)),                   # 1024 ragged tiles: the least conv3x3_ws accepts; two events
+}
+TILE_VARIANTS = ("ccbn", "ccbn_up", "mask", "bnb")
+
+
+def tile_variant_launch(dev, C, N, Hh, Ww, variant, flags, events):
+    """One launch of a TILE_PAIRS shape on seeded operands: BatchNorm prologue + ReLU + statistics (`ccbn`), the same on an up-sampled
+    source (`ccbn_up`), ReLU-mask dgrad (`mask`), BatchNorm-backward dgrad (`bnb`).  Returns (out, raw statistics or None); the
+    statistics buffer has one slot per block of a group, so every slot has a single adder."""
+    import ops
+    g = torch.Generator(device="cpu").manual_seed(1000 + C + Hh + len(variant))
+    up = variant == "ccbn_up"
+    Hs, Ws = (Hh // 2, Ww // 2) if up else (Hh, Ww)
+    x = torch.randn(N, Hs, Ws, C, generator=g).to(dev).to(BF)
+    kpad = ops._kpad(9 * C)
+    w = torch.zeros(C, kpad)
+    w[:, :9 * C] = torch.randn(C, 9 * C, generator=g) / math.sqrt(9 * C)
+    w = w.to(dev).to(BF)
+    bias = (0.1 * torch.randn(C, generator=g)).to(dev)
+    sc = (1 + 0.3 * torch.randn(N, C, generator=g)).to(dev)
+    sh = (0.2 * torch.randn(N, C, generator=g)).to(dev)
+    xin = (torch.randn(N, Hh, Ww, C, generator=g) * 1.3 + 0.2).to(dev).to(BF)      # ReLU mask / BatchNorm input
+    out = torch.full((N, Hh, Ww, C), float("nan"), device=dev, dtype=BF)
+    if variant in ("ccbn", "ccbn_up"):
+        st = ops._conv_launch(x, C, Hs, Ws, int(up), sc, sh, C, True, N, Hh, Ww, C, C, 9, kpad, w, bias, None, 0, 0, 0, None, 0, None, out,
+                              True, npe=N // events, flags=flags)
+    elif variant == "mask":
+        st = ops._conv_launch(x, C, Hs, Ws, 0, None, None, 0, False, N, Hh, Ww, C, C, 9, kpad, w, None, None, 0, 0, 0, None, 0, xin, out,
+                              None, flags=flags)
+    else:
+        st = ops._conv_launch(x, C, Hs, Ws, 0, None, None, 0, False, N, Hh, Ww, C, C, 9, kpad, w, None, None, 0, 0, 0, None, 0, xin, out,
+                              True, npe=1, flags=flags, bnb=(sc, sh, C, True))
+    return out, st
+
+
+@pytest.mark.parametrize("pair", list(TILE_PAIRS))
+def test_3x3_tile_kernels_agree_bit_for_bit(dev, pair):
+    """The same launch through two 3x3 tile-kernel families (conv3x3_lds in its three forms / conv3x3_ws against conv3x3_halo).  Every
+    family accumulates each output element over the same k-steps in the same order, so the outputs must agree bit for bit; the folded
+    statistics (per group: events, or images for the BatchNorm-backward accumulators) to 1e-5 relative, norm of the difference over the
+    norm of the reference vector -- the block partials are added in a different order.  This pins the request, prologue, swizzle,
+    K-loop and pixel-mapping code the families share (conv3x3_tile.h) against conv3x3_halo's own copy of it."""
+    import _hip
+    C, N, Hh, Ww, first, events, bnb_hw = TILE_PAIRS[pair]
+    for variant in TILE_VARIANTS:
+        hw = bnb_hw if variant == "bnb" else (Hh, Ww)
+        res = [tile_variant_launch(dev, C, N, hw[0], hw[1], variant, fl, events)
+               for fl in (getattr(_hip, first) if first else 0, _hip.CONV_NO_LDS_WEIGHTS)]
+        (o1, s1), (o0, s0) = res
+        assert torch.isfinite(o0.float()).all() and torch.isfinite(o1.float()).all(), (pair, variant)
+        nd = int((o1 != o0).sum())
+        print(f"{pair} {variant}: differing outputs {nd} of {o0.numel()}")
+        assert torch.equal(o1, o0), (pair, variant, nd, float((o1.float() - o0.float()).abs().max()))
+        if s1 is not None:
+            f1, f0 = s1.sum(1).double(), s0.sum(1).double()             # [groups, 2, C]
+            for k in range(2):
+                r = float((f1[:, k] - f0[:, k]).norm() / max(float(f0[:, k].norm()), 1e-30))
+                print(f"{pair} {variant}: statistics row {k} rel {r:.2e}")
+                assert float(f0[:, k].abs().max()) > 0 and r <= 1e-5, (pair, variant, k, r)
 
 
 def test_ws_kernel_affine_prologue_and_event_statistics(dev):
