@@ -106,6 +106,7 @@ _SIGS = {
     "ieagan_conv_stats_slots": [C.POINTER(ConvDesc)],
     "ieagan_d_stem_fwd": [C.POINTER(DStemDesc), vp],
     "ieagan_d_stem_bwd": [C.POINTER(DStemDesc), vp],
+    "ieagan_d_stem_dimg": [vp, vp, vp, vp, vp, i, i, i, vp],
     "ieagan_effgrad": [vp, vp, vp, vp, vp, l, i, i, vp],
     "ieagan_prologue_bwd": [vp, vp, i, vp, vp, i, i, i, vp, vp, vp, i, i, i, i, vp, i, i, i, i, vp],
     "ieagan_bn_finalize_fwd": [vp, f, vp, vp, i, i, f, f, i, vp, vp, vp, vp, vp, i, i, i, i, vp, vp],

@@ -112,10 +112,11 @@ class ExecOptions:
     fuse_bn_backward    BatchNorm-apply backward inside the dgrad epilogue (False: the stand-alone prologue_bwd pass)
     fuse_shortcut_grad  residual-shortcut gradients added inside the dx-producing kernel (False: autograd adds)
     fuse_1x1_backward / fuse_3x3_backward (+ *_min_pixels)   the whole-backward kernels conv1x1_bwd / conv3x3_bwd (False: separate launches)
-    fuse_d_stem         D.input_conv + the first DBlock's conv1 / conv_sc / pooled shortcut in one launch each way"""
+    fuse_d_stem         D.input_conv + the first DBlock's conv1 / conv_sc / pooled shortcut in one launch each way
+    fuse_d_stem_dimg    d img of the fused stem (the pass that trains G) in one launch (False: conv1's dgrad + conv_Cto1, dh0 through HBM)"""
     FIELDS = dict(wgrad_side_stream=True, two_stage_wgrad=True, fuse_bn_backward=True, fuse_shortcut_grad=True,
                   fuse_1x1_backward=True, fuse_1x1_min_pixels=1 << 16, fuse_3x3_backward=True, fuse_3x3_min_pixels=1 << 16,
-                  fuse_d_stem=True)
+                  fuse_d_stem=True, fuse_d_stem_dimg=True)
     __slots__ = tuple(FIELDS)
 
     def __init__(self, like=None, **kw):
@@ -1232,8 +1233,13 @@ class DStemFn(torch.autograd.Function):
             H.call("ieagan_d_stem_bwd", d, H.stream())
             dW_in, db_in = sn_backward(dw_in, w_in, rec_in, cs_in, b_in)
             dW1, db1 = sn_backward(dw1, w1, rec1, cs1, b1)
-        if need[0]:
-            # the pass that trains G: d img = input_conv^T (dh1 W1 + 0.25 expand(d p0)) through the generic launches
+        if need[0] and opts_of(rec_in).fuse_d_stem_dimg:
+            # the pass that trains G: d img = input_conv^T (dh1 W1 + 0.25 expand(d p0)) in one launch, dh0 in registers only
+            dimg = torch.empty(N, 1, Hh, Ww, dtype=torch.float32, device=dev)
+            H.call("ieagan_d_stem_dimg", dh1.data_ptr(), dpt.data_ptr(), rec1.w_bwd.data_ptr(), rec_in.w_plain.data_ptr(), dimg.data_ptr(), N, Hh, Ww,
+                   H.stream())
+        elif need[0]:
+            # the same through the generic launches (dh0 written and read back)
             dh0 = torch.empty(N, Hh, Ww, 32, dtype=BF16, device=dev)
             _dgrad(types.SimpleNamespace(rec=rec1, N=N, Hc=Hh, Wc=Ww, Cout=16, Cin=32, taps=1), dh1, 16, dh0, link=(dpt, 32, 32), link_rs=1,
                    link_scale=0.25)

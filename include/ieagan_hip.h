@@ -276,7 +276,7 @@ int ieagan_wgrad_c1(const float* img, const float* tanh_y, const void* t, const 
  *   fwd:  img fp32 [N,H,W] -> h1 = conv1(h0) bf16 [N,H,W,16], p0 = AvgPool2d(h0) bf16 [N,H/2,W/2,32], sc = conv_sc(p0) bf16 [N,H/2,W/2,32],
  *         h0 = input_conv(img) recomputed on chip, never stored;
  *   bwd:  dh0 = dh1 W1 + 0.25 expand(dp0) (LDS only) -> dw_in [9][32] += , db_in [32][32 replicas] +=, dw1 [16][32] +=, db1 [32][16] +=
- *         (weight gradients only: the pass that needs d img keeps the generic launches).
+ *         (weight gradients only: the pass that needs d img has ieagan_d_stem_dimg).
  * w_in fp32 [9][32] (tap-major, / sigma), w1 / wsc the bf16 forward packs [Cout][32], w1_bwd the transposed pack [32][32].  H % 8 == 0, W % 32 == 0. */
 typedef struct {
     const float* img;
@@ -300,6 +300,11 @@ typedef struct {
 } ieagan_d_stem_desc;
 int ieagan_d_stem_fwd(const ieagan_d_stem_desc* d, void* stream);
 int ieagan_d_stem_bwd(const ieagan_d_stem_desc* d, void* stream);
+/* The pass that needs d img and no weight gradients (G's step), in one launch: dimg fp32 [N,H,W] = input_conv^T (dh1 W1 + 0.25 expand(dp0)),
+ * dh0 rounded to bf16 as the separate launches stored it and formed in registers only.  dh1 bf16 [N,H,W,16], dp0 bf16 [N,H/2,W/2,32],
+ * w1_bwd and w_in as above.  No bias, no tanh; the taps are flipped as ieagan_conv_Cto1(..., flip = 1) flips them. */
+int ieagan_d_stem_dimg(const void* dh1, const void* dp0, const void* w1_bwd, const float* w_in, float* dimg, int N, int H, int W,
+                       void* stream);
 
 /* ---- batched spectral norm (sn.hip): layers.SN.W_ / power_iteration (layers.py:89-165) -------- */
 int ieagan_sn_forward(const long* table, const int* blocks, int nblocks, const int* cblocks, int ncblocks,

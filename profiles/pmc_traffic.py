@@ -18,6 +18,7 @@ def family(name):
     if n.startswith("conv3x3_bwd_kernel"): return "conv3x3_bwd"
     if n.startswith("d_stem_fwd_kernel"): return "d_stem_fwd"
     if n.startswith("d_stem_bwd_kernel"): return "d_stem_bwd"
+    if n.startswith("d_stem_dimg_kernel"): return "d_stem_dimg"
     if n.startswith("wgrad_reduce_kernel"): return "conv3x3_wgrad"
     if n.startswith("conv_gather_kernel<9"): return "conv3x3_gather"
     if n.startswith("conv3x3_halo_kernel"): return "conv3x3_halo"
