@@ -1,7 +1,8 @@
 """The PXD detector surface, this project's own (no counterpart in the reference's ``utils``): detector-level validation statistics
 (csrc/pxd_stats.hip), event production as sparse digits (csrc/pxd_digits.hip), clusters of the digits and their spectra
-(csrc/pxd_clusters.hip), cluster reconstruction -- cuts, charge-weighted positions, per-sensor position maps (csrc/pxd_reco.hip) -- and the
-event file of ``produce.py``.  ``utils`` re-exports every name defined here."""
+(csrc/pxd_clusters.hip), cluster reconstruction -- cuts, charge-weighted positions, per-sensor position maps (csrc/pxd_reco.hip) --, the
+event file of ``produce.py`` and the store that keeps such a file's events on the device and expands them into the network input
+(csrc/pxd_events.hip).  ``utils`` re-exports every name defined here."""
 from __future__ import annotations
 
 import numpy as np
@@ -571,3 +572,227 @@ def read_digits(path):
     for e in range(off.size - 1):
         s = slice(int(off[e]), int(off[e + 1]))
         yield (sensor[s].tolist(), ucell[s].tolist(), vcell[s].tolist()), charge[s].tolist()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# sparse event store: the events of a digit file resident on the device, expanded into the network input (csrc/pxd_events.hip)
+# ---------------------------------------------------------------------------------------------------------
+def _event_of(event_offsets, k):
+    """The event that holds digit ``k``."""
+    return int(np.searchsorted(event_offsets, k, side="right") - 1)
+
+
+def event_columns(event_offsets, sensor, ucell, vcell, charge, shape=(250, 768), n_sensors=40, who="PXDEventStore"):
+    """The host half of ``PXDEventStore``: the columns of an event file -> ``(offsets int64 [events + 1], pos int32 [D], charge uint8 [D])``
+    with ``pos = (sensor * H + ucell) * W + vcell``, after every check of the store's contract, in NumPy and without a device call.
+    ``ValueError`` -- naming the first offending event -- for offsets that do not start at 0 or decrease, column lengths that disagree, a
+    sensor / ucell / vcell outside the geometry, a charge of 0, and positions that are not strictly ascending inside an event (unsorted or
+    duplicate digits)."""
+    Hh, Ww = (int(v) for v in shape)
+    S = int(n_sensors)
+    if S <= 0 or Hh <= 0 or Ww <= 0 or S * Hh * Ww >= 2 ** 31:
+        raise ValueError(f"{who}: {S} sensors of {Hh} x {Ww} pixels are no geometry whose positions fit int32")
+    off = np.asarray(event_offsets)
+    if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError(f"{who}: event_offsets must be a 1-D integer array of events + 1 entries")
+    off = off.astype(np.int64)
+    if off[0] != 0:
+        raise ValueError(f"{who}: event_offsets starts at {off[0]}, not at 0")
+    down = np.nonzero(np.diff(off) < 0)[0]
+    if down.size:
+        raise ValueError(f"{who}: event_offsets decreases at event {int(down[0])} ({off[down[0]]} -> {off[down[0] + 1]})")
+    cols = dict(sensor=np.asarray(sensor), ucell=np.asarray(ucell), vcell=np.asarray(vcell), charge=np.asarray(charge))
+    for k, v in cols.items():
+        if v.ndim != 1 or v.size != off[-1]:
+            raise ValueError(f"{who}: {k} has {v.size} entries, event_offsets ends at {off[-1]}")
+        if v.size and not np.issubdtype(v.dtype, np.integer):
+            raise ValueError(f"{who}: {k} is {v.dtype}, not an integer column")
+    for k, limit in (("sensor", S), ("ucell", Hh), ("vcell", Ww)):
+        bad = np.nonzero((cols[k] < 0) | (cols[k] >= limit))[0]
+        if bad.size:
+            raise ValueError(f"{who}: event {_event_of(off, bad[0])}: {k} = {int(cols[k][bad[0]])} of digit {int(bad[0])} is outside 0 .. {limit - 1}")
+    bad = np.nonzero((cols["charge"] <= 0) | (cols["charge"] > 255))[0]
+    if bad.size:
+        raise ValueError(f"{who}: event {_event_of(off, bad[0])}: charge = {int(cols['charge'][bad[0]])} of digit {int(bad[0])} is outside 1 .. 255")
+    pos = ((cols["sensor"].astype(np.int64) * Hh + cols["ucell"]) * Ww + cols["vcell"]).astype(np.int32)
+    if pos.size > 1:
+        step = np.diff(pos) <= 0
+        starts = off[1:-1]
+        step[starts[(starts > 0) & (starts < pos.size)] - 1] = False          # the first digit of an event follows nothing
+        bad = np.nonzero(step)[0]
+        if bad.size:
+            k = int(bad[0]) + 1
+            raise ValueError(f"{who}: event {_event_of(off, k)}: digit {k} (position {int(pos[k])}) does not lie behind digit {k - 1} (position "
+                             f"{int(pos[k - 1])}): the digits of an event must be sorted by (sensor, ucell, vcell) without duplicates")
+    return off, pos, cols["charge"].astype(np.uint8)
+
+
+def select_events(event_offsets, events, *columns):
+    """``(offsets, *columns)`` of the events ``events`` (numbers into ``event_offsets``, any order, repeats allowed) of a digit list."""
+    off = np.asarray(event_offsets, np.int64)
+    ev = np.asarray(events, np.int64).reshape(-1)
+    if ev.size and (ev.min() < 0 or ev.max() >= off.size - 1):
+        raise ValueError(f"PXDEventStore: events= holds {int(ev.min())} .. {int(ev.max())}, the file has {off.size - 1} events")
+    counts = (off[1:] - off[:-1])[ev]
+    new = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    take = np.repeat(off[:-1][ev] - new[:-1], counts) + np.arange(new[-1], dtype=np.int64)
+    return (new,) + tuple(np.asarray(c)[take] for c in columns)
+
+
+def read_event_columns(path, shape=(250, 768), n_sensors=40, events=None):
+    """The host half of ``PXDEventStore.from_file``: the file of ``write_digits`` -> checked ``(offsets, pos, charge)`` of ``event_columns``,
+    of all events or of the subset ``events``."""
+    with np.load(path) as t:
+        missing = [k for k in ("event_offsets", "sensor", "ucell", "vcell", "charge") if k not in t.files]
+        if missing:
+            raise ValueError(f"PXDEventStore: {path} is no event file of write_digits, it lacks {missing}")
+        off, sensor, ucell, vcell, charge = (t[k] for k in ("event_offsets", "sensor", "ucell", "vcell", "charge"))
+    off, pos, charge = event_columns(off, sensor, ucell, vcell, charge, shape, n_sensors, who=f"PXDEventStore ({path})")
+    return (off, pos, charge) if events is None else select_events(off, events, pos, charge)
+
+
+def split_positions(pos, shape=(250, 768)):
+    """Positions of a store -> the ``(sensor, ucell, vcell)`` columns of the event file."""
+    Hh, Ww = shape
+    s, rest = np.divmod(np.asarray(pos, np.int64), Hh * Ww)
+    u, v = np.divmod(rest, Ww)
+    return s, u, v
+
+
+def event_file_length(path):
+    """Number of events in a file of ``write_digits`` (reads the offsets only)."""
+    with np.load(path) as t:
+        return int(t["event_offsets"].size - 1)
+
+
+class PXDEventStore:
+    """Events of sparse PXD digits resident on the device: ``pos`` int32 ``[D]`` (``(sensor * H + ucell) * W + vcell``, strictly ascending
+    inside an event), ``charge`` uint8 ``[D]``, ``offsets`` int64 ``[events + 1]`` -- about 5 bytes a digit, 0.4 MB for a 40 x 250 x 768 event at
+    1 % occupancy against 7.7 MB dense.  ``ingest`` / ``dense`` expand E events in one HIP launch (csrc/pxd_events.hip) on the current
+    stream: no file read, no host-to-device copy and, with a device id tensor, no synchronisation.  Build one with ``from_file`` (the
+    ``produce.py`` / ``write_digits`` format), ``from_arrays`` or ``from_dense``; every check of the contract runs on the host before the
+    upload (``event_columns``)."""
+
+    def __init__(self, offsets, pos, charge, shape=(250, 768), n_sensors=40, device=None):
+        """Checked host columns (``event_columns``) -> the device.  Use the ``from_*`` constructors."""
+        if device is not None and torch.device(device).type != "cuda":
+            raise RuntimeError(f"PXDEventStore lives on a HIP device, not on {device}: there is no CPU path")
+        H.require_gpu()
+        self.shape, self.n_sensors = (int(shape[0]), int(shape[1])), int(n_sensors)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        self.counts = np.diff(offsets)
+        self.offsets = torch.from_numpy(offsets).to(self.device)
+        self.pos = torch.from_numpy(np.ascontiguousarray(pos, np.int32)).to(self.device)
+        self.charge = torch.from_numpy(np.ascontiguousarray(charge, np.uint8)).to(self.device)
+
+    @classmethod
+    def from_arrays(cls, event_offsets, sensor, ucell, vcell, charge, shape=(250, 768), n_sensors=40, device=None):
+        return cls(*event_columns(event_offsets, sensor, ucell, vcell, charge, shape, n_sensors), shape, n_sensors, device)
+
+    @classmethod
+    def from_file(cls, path, shape=(250, 768), n_sensors=40, events=None, device=None):
+        """The event file of ``produce.py`` / ``write_digits``; ``events``: the event numbers to keep (a rank's shard), chosen before the upload."""
+        return cls(*read_event_columns(path, shape, n_sensors, events), shape, n_sensors, device)
+
+    @classmethod
+    def from_dense(cls, events, n_sensors=40, device=None):
+        """Dense uint8 events (arrays or tensors ``[k * n_sensors, H, W]``, or ``*.npy`` paths) -> a store.  Every item goes through
+        ``pxd_digits`` (threshold 0: every nonzero charge), so it is compacted on the device and only its digits are kept."""
+        if isinstance(events, (str, np.ndarray, torch.Tensor)):
+            events = [events]
+        pos, charge, counts, shape = [], [], [], None
+        for ev in events:
+            name = ev if isinstance(ev, str) else "<array>"
+            ev = np.load(ev) if isinstance(ev, str) else ev
+            x = ev if isinstance(ev, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ev))
+            if x.dtype != torch.uint8 or x.dim() != 3:
+                raise TypeError(f"PXDEventStore.from_dense: {name} is {tuple(x.shape)} {x.dtype}, not uint8 [k * n_sensors, H, W]")
+            if shape not in (None, tuple(x.shape[1:])):
+                raise ValueError(f"PXDEventStore.from_dense: {name} has images of {tuple(x.shape[1:])}, the events before it of {shape}")
+            shape = tuple(x.shape[1:])
+            if device is not None and not x.is_cuda:
+                x = x.to(device)
+            index, chg, cnt = pxd_digits(x, threshold=0.0, n_sensors=n_sensors).cpu()
+            per = int(n_sensors) * shape[0] * shape[1]
+            pos.append((index.astype(np.int64) % per).astype(np.int32))
+            charge.append(chg)
+            counts.append(cnt.reshape(-1, int(n_sensors)).sum(1))
+        if shape is None:
+            raise ValueError("PXDEventStore.from_dense: no events")
+        offsets = np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.int64)
+        return cls(offsets, np.concatenate(pos), np.concatenate(charge), shape, n_sensors, device)
+
+    def __len__(self):
+        return int(self.counts.size)
+
+    @property
+    def nbytes(self):
+        """Bytes the store holds on the device."""
+        return int(self.pos.numel() * 4 + self.charge.numel() + self.offsets.numel() * 8)
+
+    def columns(self):
+        """NumPy ``(event_offsets, sensor, ucell, vcell, charge)``: the columns of the event file (one read-back)."""
+        s, u, v = split_positions(self.pos.cpu().numpy(), self.shape)
+        return self.offsets.cpu().numpy(), s, u, v, self.charge.cpu().numpy()
+
+    def save(self, path):
+        """Writes the store as an event file (``write_digits``)."""
+        write_digits(path, *self.columns())
+
+    def _ids(self, event_ids, who):
+        """``event_ids`` -> int32 device tensor ``[E]``.  An int or a sequence is range-checked here and uploaded; an int32 tensor on the store's
+        device is taken as it is -- nothing crosses PCIe, nothing synchronises, and an id outside the store then gives an empty event."""
+        if isinstance(event_ids, torch.Tensor) and event_ids.is_cuda:
+            if event_ids.dtype != torch.int32 or event_ids.dim() != 1 or event_ids.device != self.device:
+                raise TypeError(f"{who}: a device id tensor must be int32 [E] on {self.device}, got {event_ids.dtype} "
+                                f"{tuple(event_ids.shape)} on {event_ids.device}")
+            ids = event_ids.contiguous()
+        else:
+            host = np.asarray(event_ids.numpy() if isinstance(event_ids, torch.Tensor) else event_ids)
+            if host.dtype.kind not in "iu" or host.ndim > 1:
+                raise TypeError(f"{who}: event_ids must be an int, a sequence of ints or an int32 device tensor")
+            host = host.reshape(-1).astype(np.int64)
+            if host.size and (host.min() < 0 or host.max() >= len(self)):
+                raise IndexError(f"{who}: event ids {int(host.min())} .. {int(host.max())} outside the store's 0 .. {len(self) - 1}")
+            ids = torch.from_numpy(host.astype(np.int32)).to(self.device)
+        E = int(ids.numel())
+        if E == 0 or E * self.n_sensors > 65535:
+            raise ValueError(f"{who}: {E} event(s) of {self.n_sensors} sensors: one call takes 1 .. {65535 // self.n_sensors} events")
+        return ids, E
+
+    def _store_args(self, ids, E):
+        return (H.ptr(self.pos) or None, H.ptr(self.charge) or None, self.offsets.data_ptr(), int(self.pos.numel()), len(self), ids.data_ptr(), E,
+                self.n_sensors, self.shape[0], self.shape[1])
+
+    def ingest(self, event_ids, noise=None, scale=4e-3, pad=3):
+        """The network input of the events ``event_ids``: fp32 ``[E * n_sensors, 1, H + 2*pad, W]``, bit for bit what ``utils.ingest_event``
+        gives on their dense uint8 images.  ``noise`` as there: explicit U[0,1) draws ``[E * n_sensors, H + 2*pad, W]``; None = drawn on the
+        device; False = no dequantisation noise."""
+        ids, E = self._ids(event_ids, "PXDEventStore.ingest")
+        pad = int(pad)
+        if pad < 0:
+            raise ValueError("PXDEventStore.ingest: pad is negative")
+        N, (Hh, Ww) = E * self.n_sensors, self.shape
+        with torch.cuda.device(self.device):
+            out = torch.empty(N, 1, Hh + 2 * pad, Ww, dtype=torch.float32, device=self.device)
+            if noise is None:
+                noise = torch.rand(N, Hh + 2 * pad, Ww, device=self.device)
+            elif noise is False:
+                noise = None
+            else:
+                noise = noise.to(self.device, torch.float32).contiguous()
+                if noise.numel() != out.numel():
+                    raise ValueError("noise must have the padded shape [E * n_sensors, H + 2*pad, W]")
+            H.call("ieagan_pxd_event_ingest", *self._store_args(ids, E), pad, H.ptr(noise), float(scale), out.data_ptr(), H.stream())
+        return out
+
+    def dense(self, event_ids):
+        """The dense uint8 images ``[E * n_sensors, H, W]`` of the events ``event_ids``: the input of every ``PXD*`` accumulator."""
+        ids, E = self._ids(event_ids, "PXDEventStore.dense")
+        with torch.cuda.device(self.device):
+            out = torch.empty(E * self.n_sensors, *self.shape, dtype=torch.uint8, device=self.device)
+            H.call("ieagan_pxd_event_dense", *self._store_args(ids, E), out.data_ptr(), H.stream())
+        return out

@@ -9,7 +9,9 @@ metric / singular-value logging and periodic checkpoints in the reference's file
 
 Data: ``--dataroot DIR`` with one ``*.npy`` per event (uint8 ``[40, 250, 768]`` detector images, or float32
 already in [-1, 1]); the pad(3 rows) -> lognorm255 -> +4e-3 U dequantisation -> [-1, 1] chain of the
-reference's loader (utils/dataloader.py:59-76, utils/norm.py:8-19) runs on the GPU.  ``--synthetic N`` trains on
+reference's loader (utils/dataloader.py:59-76, utils/norm.py:8-19) runs on the GPU.  ``--dataroot FILE.npz``: a digit file
+(``produce.py`` / ``pack_events.py``); the rank's shard is uploaded once into a ``utils.PXDEventStore`` and every step expands its events
+on the device (no file read, no host-to-device copy of the input).  ``--synthetic N`` trains on
 N generated events (no files).  ``--val_every K`` (uint8 events) runs the detector-level validation of
 ``train_fns.validate`` on rank 0 every K iterations (``logs/validation_rank0.jsonl``).  Any default of
 ``defaults.default_config()`` can be overridden as ``--key value``.
@@ -88,6 +90,11 @@ def to_network_range(ev: torch.Tensor, res_h: int) -> torch.Tensor:
     return ev.float().unsqueeze(1).contiguous()
 
 
+def is_event_file(path):
+    """``--dataroot`` names a digit file (``.npz``) instead of a directory of dense ``*.npy`` events."""
+    return bool(path) and path.endswith(".npz") and os.path.isfile(path)
+
+
 def run(cfg):
     rank, world, local = parallel.init_from_env()
     if world > 1:
@@ -127,6 +134,10 @@ def run(cfg):
     h, w = cfg["resolution"], cfg["resolution"] * cfg["H_base"]
     if cfg["synthetic"]:
         events = [synthetic_event(cfg["n_classes"], h - 6, w, cfg["seed"] + i) for i in range(cfg["synthetic"])]
+    elif is_event_file(cfg["dataroot"]):
+        events = list(range(utils.event_file_length(cfg["dataroot"])))      # event numbers: sharded like the files below
+        if not events:
+            raise SystemExit(f"{cfg['dataroot']} holds no events")
     else:
         files = sorted(glob.glob(os.path.join(cfg["dataroot"] or "", "*.npy")))
         if not files:
@@ -144,6 +155,11 @@ def run(cfg):
     E = max(int(cfg.get("events_per_step", 1) or 1), 1)
     if len(mine) < E:
         raise SystemExit(f"events_per_step={E} but this rank holds only {len(mine)} event(s)")
+    store = None
+    if not cfg["synthetic"] and is_event_file(cfg["dataroot"]):
+        # the rank's shard of the digit file, resident on the device; from here on `mine` numbers the events of the store
+        store = utils.PXDEventStore.from_file(cfg["dataroot"], shape=(h - 6, w), n_sensors=cfg["n_classes"], events=mine, device=dev)
+        mine = list(range(len(store)))
     z_, y_ = utils.prepare_z_y(max(cfg["G_batch_size"], cfg["batch_size"]) * E, G.dim_z, cfg["n_classes"], device=dev,
                                z_dist=cfg["z_dist"], threshold=cfg["truncated_threshold"])
     train = train_fns.GAN_training_function(G, D, GD, z_, y_, ema, state, cfg, dev)
@@ -154,6 +170,9 @@ def run(cfg):
         # the real side of the detector-level validation, once: the first min(val_events, len(events)) events of this rank
         real_acc = utils.PXDStatistics(n_sensors=cfg["n_classes"], threshold=cfg["val_threshold"], device=dev)
         for ev in mine[:min(cfg["val_events"], len(mine))]:
+            if store is not None:
+                real_acc.update(store.dense(ev))
+                continue
             ev = ev if isinstance(ev, np.ndarray) else np.load(ev)
             if ev.dtype != np.uint8:
                 raise SystemExit(f"val_every > 0 needs uint8 detector events (ADC counts); got {ev.dtype} events already in network "
@@ -171,15 +190,19 @@ def run(cfg):
     stop = False
     for epoch in range(state["epoch"], cfg["num_epochs"]):
         order = np.random.permutation(len(mine)) if cfg["shuffle"] else np.arange(len(mine))
+        perm = None if store is None else torch.from_numpy(order.astype(np.int32)).to(dev)      # the epoch's order, uploaded once
         for s0 in range(0, len(order) - E + 1, E):
             state["itr"] += 1
             G.train()
             D.train()
             if G_ema is not None:
                 G_ema.train()
-            evs = [mine[i] if isinstance(mine[i], np.ndarray) else np.load(mine[i]) for i in order[s0:s0 + E]]
-            x = torch.cat([to_network_range(torch.from_numpy(ev), h).to(dev) for ev in evs]) if E > 1 else \
-                to_network_range(torch.from_numpy(evs[0]), h).to(dev)
+            if store is not None:
+                x = store.ingest(perm[s0:s0 + E], pad=3)        # device ids: no copy and no synchronisation for the input
+            else:
+                evs = [mine[i] if isinstance(mine[i], np.ndarray) else np.load(mine[i]) for i in order[s0:s0 + E]]
+                x = torch.cat([to_network_range(torch.from_numpy(ev), h).to(dev) for ev in evs]) if E > 1 else \
+                    to_network_range(torch.from_numpy(evs[0]), h).to(dev)
             metrics = train(x, y)
             if log is not None:
                 rec = dict(itr=state["itr"], **metrics)

@@ -494,6 +494,28 @@ int ieagan_pxd_cluster_maps(const int* cluster, const int* accepted_total, const
                             const int* digit_total, int N, int H, int W, int n_sensors, long capacity, unsigned long long* count,
                             unsigned long long* charge, unsigned long long* overflow, void* stream);
 
+/* ---- sparse event store -> network input (pxd_events.hip) --------------------------------------------
+ * A store holds n_events events of PXD digits on the device (the columns of the produce.py file, flattened):
+ *   pos [n_digits] int32       (sensor * H + ucell) * W + vcell of a digit inside its event, STRICTLY ascending inside an event;
+ *                              S * H * W < 2^31
+ *   charge [n_digits] uint8    each > 0
+ *   offsets [n_events + 1] int64   the digits of event i are [offsets[i], offsets[i + 1])
+ * event_ids [E] int32 is read ON THE DEVICE: output images [e * S, (e + 1) * S) are the S sensors of event event_ids[e] (any order,
+ * repeats allowed); an id outside [0, n_events) is an empty event -- background only -- and offsets is not read for it.
+ *   ieagan_pxd_event_ingest   out fp32 [E*S, 1, H + 2 pad, W]: exactly what ieagan_event_ingest gives on the dense uint8 images [E*S, H, W] of
+ *                             those events with the same noise (fp32 [E*S, H + 2 pad, W] or NULL), scale and pad -- the same float
+ *                             expression in the same order, equal bit for bit
+ *   ieagan_pxd_event_dense    out uint8 [E*S, H, W]: those dense images themselves (the input of the ieagan_pxd_* entry points above)
+ * Every output element is stored exactly once (nothing is filled and then overwritten); E * S <= 65535.  Memory safety does not depend on
+ * the content of the store: offsets are clipped to [0, n_digits], a digit is placed only after its position has been checked, and a store
+ * that breaks the contract above gives wrong pixels, never a wrong address.  No atomics, no float reduction, no scratch: two calls write
+ * the same bytes.  One launch on `stream`, no synchronise, no copy (graph-capturable; a replay reads the current content of event_ids). */
+int ieagan_pxd_event_ingest(const int* pos, const unsigned char* charge, const long* offsets, long n_digits, int n_events,
+                            const int* event_ids, int E, int S, int H, int W, int pad, const float* noise, float scale, float* out,
+                            void* stream);
+int ieagan_pxd_event_dense(const int* pos, const unsigned char* charge, const long* offsets, long n_digits, int n_events,
+                           const int* event_ids, int E, int S, int H, int W, unsigned char* out, void* stream);
+
 /* ---- orthogonal regularisation (ortho.hip) -------------------------------------------------------
  * Replaces utils.ortho (reference utils/__init__.py:843-859) for ALL weight matrices of a network in one call:
  * grad[l] += 2*strength * ((W_l W_l^T) (.) (1 - I)) W_l, fp32, on the flat parameter / gradient arenas.
