@@ -91,10 +91,9 @@ def produce(G, cfg, n_events, per_batch, seed, threshold=0.0):
 
     def finish(d):
         index, charge, counts = d.cpu()         # copies out of the pinned buffers, which the batch after next reuses
-        copied = d._host[3]
         stats["waits"] += 1
-        stats["extra_copies"] += int(index.size > copied)
-        stats["bytes_copied"] += 4 * (d.shape[0] + 1) + 5 * max(copied, index.size)
+        stats["extra_copies"] += int(index.size > d.copied)
+        stats["bytes_copied"] += 4 * (d.shape[0] + 1) + 5 * max(d.copied, index.size)
         stats["last"] = index.size
         found.append((index, charge))
         per_event.append(counts.reshape(-1, n).sum(1))

@@ -31,6 +31,89 @@ def _ptrs(capacity, *tensors):
     return [t.data_ptr() if capacity else None for t in tensors]
 
 
+def _header(N, device):
+    """The int32 header ``[N + 1]`` every launch of the chain fills -- ``counts [N]``, then ``total [1]`` -- and its two device pointers."""
+    header = torch.empty(N + 1, dtype=torch.int32, device=device)
+    return header, header.data_ptr(), header.data_ptr() + 4 * N
+
+
+def pxd_read_back(**tensors):
+    """One packed read-back: the named tensors (any dtypes, shapes and lengths, empty ones included) as bytes in one tensor on their
+    device, one copy to the host, one wait -> dict of NumPy arrays by name, each in its tensor's dtype and shape, bit for bit.  The widest
+    elements are packed first, so every column starts at a multiple of its element size; each array is a copy that owns its memory."""
+    order = sorted(tensors.items(), key=lambda kt: -kt[1].element_size())
+    host = torch.cat([t.contiguous().reshape(-1).view(torch.uint8) for _, t in order]).cpu()      # the one device-to-host copy
+    parts = host.split([t.numel() * t.element_size() for _, t in order])
+    return {k: p.view(t.dtype).numpy().reshape(tuple(t.shape)).copy() for (k, t), p in zip(order, parts)}
+
+
+class _PXDProduct:
+    """What the device-side results of the chain (digits -> clusters -> positions) share: the ``counts`` / ``total`` views of their header
+    and the rule that the host never sees a truncated event.  A subclass says how the chain is run again (``_again(capacity)``)."""
+
+    def _set_header(self, header, source=None):
+        if source is not None:          # the product before this one: its images, geometry, capacity and threshold hold
+            vars(self).update((k, getattr(source, k)) for k in ("images", "capacity", "n_sensors", "shape", "threshold"))
+        self.header, self.counts, self.total = header, header[:self.shape[0]], header[self.shape[0]:]
+
+    def _grow(self, total):
+        """The digit total exceeds the capacity: the chain is run again with ``capacity = total`` and its result adopted."""
+        vars(self).update((k, v) for k, v in vars(self._again(total)).items() if not k.startswith("_"))
+
+    def _host_columns(self, columns):
+        """``pxd_read_back`` of the tensors ``columns()``, ``digit_header`` among them; after ``_grow`` if need be (a second read-back then)."""
+        host = pxd_read_back(**columns())
+        if host["digit_header"][-1] > self.capacity:
+            self._grow(int(host["digit_header"][-1]))
+            host = pxd_read_back(**columns())
+        return host
+
+
+class _PXDAccumulator:
+    """What the three accumulators share: the fields, the ``update`` preamble (input, device, image size), the ``result`` preamble (one
+    packed read-back, the overflow refusal) and the per-image tables ``[events, S]``.  A subclass names its device table (``_table``; with
+    ``_overflow`` its last word counts the updates that held more digits than the capacity) and its per-image lists (``_per_image``)."""
+    _table, _per_image, _overflow = "tables", ("clusters",), True
+
+    def __init__(self, n_sensors=40, threshold=7.0, capacity=None, device=None):
+        self.n_sensors, self.threshold, self.capacity = int(n_sensors), float(threshold), capacity if capacity is None else int(capacity)
+        self.device = torch.device(device) if device is not None else None
+        self.reset()
+
+    def reset(self):
+        vars(self).update({self._table: None, "shape": None}, **{k: [] for k in self._per_image})
+
+    def _input(self, given, who, *products):
+        """The ``update`` preamble.  Images: ``_sensor_images`` on the accumulator's device.  One of ``products`` (the results of the chain
+        this accumulator would run itself): taken as it is, after a ``ValueError`` when it was not made the way the accumulator makes it."""
+        me, product = type(self).__name__, isinstance(given, products)
+        x = given if product else _sensor_images(given, self.n_sensors, who, self.device)
+        device = x.header.device if product else x.device
+        for k in ("n_sensors", "threshold", "seed_cut", "charge_cut", "device") if product else ():
+            made, mine = (device.index, self.device and self.device.index) if k == "device" else (getattr(x, k, None), getattr(self, k, None))
+            if made != mine and None not in (made, mine):
+                raise ValueError(f"{me}.update: the {type(x).__name__} was made with {k} = {made}, not {mine}")
+        self.device = self.device or device
+        if self.shape not in (None, tuple(x.shape[1:])):
+            raise ValueError(f"{me}.update: image size {tuple(x.shape[1:])} differs from the accumulated {self.shape}")
+        self.shape = tuple(x.shape[1:])
+        return x
+
+    def _host_tables(self):
+        """The ``result`` preamble -> ``(table, {name: per-image table [events, S]})`` on the host, the overflow word taken off."""
+        who = type(self).__name__
+        if not getattr(self, self._per_image[0]):
+            raise RuntimeError(f"{who}.result() before any update()")
+        host = pxd_read_back(table=getattr(self, self._table), **{k: torch.cat(getattr(self, k)) for k in self._per_image})
+        table = host.pop("table")
+        if self._overflow and table[-1] != 0:
+            raise RuntimeError(f"{who}: {int(table[-1])} update(s) held more digits than the capacity"
+                               f"{'' if self.capacity is None else ' of %d' % self.capacity}, their clusters are truncated: "
+                               f"pass a larger capacity= to {who}")
+        per_image = {k: v.reshape(-1, self.n_sensors) for k, v in host.items()}
+        return table[:-1] if self._overflow else table, dict(per_image, n_events=host[self._per_image[0]].size // self.n_sensors)
+
+
 def _rel_err(real, fake, ok):
     """Mean over the sensors ``ok`` of |fake - real| / real (a NaN of ``fake`` counts as 0); NaN when there is no such sensor."""
     r, f = np.asarray(real, np.float64), np.nan_to_num(np.asarray(fake, np.float64), nan=0.0)
@@ -63,27 +146,18 @@ def pxd_bin_index(v):
     return np.where(v < 1, 0, np.where(v < 7, 1, 2 + np.minimum(np.floor(np.minimum(v, 255.0)) - 7, 248))).astype(np.int64)
 
 
-class PXDStatistics:
+class PXDStatistics(_PXDAccumulator):
     """Accumulator of the reference's per-event detector statistics (eval_all.py:75-101 ``get_stats``) over batches of sensor images in
     detector units, ``[N, H, W]`` fp32 (``Generator(..., export=True)``) or uint8 (event files); image ``n`` is sensor
     ``n % n_sensors``.  ``update`` is one HIP launch pair (csrc/pxd_stats.hip) on the current stream: it neither synchronises nor
     copies to the host; ``result()`` does the single read-back."""
+    _table, _per_image, _overflow = "spectrum", ("hits", "charge"), False       # spectrum: int64 [S, 251], the kernel's 64-bit counters
 
     def __init__(self, n_sensors=40, threshold=7.0, device=None):
-        self.n_sensors, self.threshold = int(n_sensors), float(threshold)
-        self.device = torch.device(device) if device is not None else None
-        self.reset()
-
-    def reset(self):
-        self.spectrum = None            # int64 [S, 251] on the device (the kernel's 64-bit unsigned counters)
-        self.hits, self.charge, self.shape = [], [], None
+        super().__init__(n_sensors, threshold, None, device)
 
     def update(self, images):
-        x = _sensor_images(images, self.n_sensors, "PXDStatistics.update", self.device)
-        self.device = self.device or x.device
-        if self.shape not in (None, tuple(x.shape[1:])):
-            raise ValueError(f"PXDStatistics.update: image size {tuple(x.shape[1:])} differs from the accumulated {self.shape}")
-        self.shape = tuple(x.shape[1:])
+        x = self._input(images, "PXDStatistics.update")
         N, Hh, Ww = x.shape
         if self.spectrum is None:
             self.spectrum = torch.zeros(self.n_sensors, H.PXD_BINS, dtype=torch.int64, device=self.device)
@@ -103,16 +177,9 @@ class PXDStatistics:
         [0, 0.02) of every per-image occupancy plus ``occ_overflow``, ``n_events``; and the per-image ``hits`` / ``charge`` ``[E, S]``.
         The occupancy bin is ``(hits * 10000) // (H*W)`` in integers: a bin edge of ``linspace(0, 0.02, 201)`` is then decided
         exactly, not by float rounding."""
-        if not self.hits:
-            raise RuntimeError("PXDStatistics.result() before any update()")
-        S = self.n_sensors
+        spectrum, per_image = self._host_tables()
+        hits, charge = per_image["hits"].astype(np.int64), per_image["charge"]
         px = self.shape[0] * self.shape[1]
-        packed = torch.cat([self.spectrum.reshape(-1), torch.cat(self.hits).to(torch.int64),
-                            torch.cat(self.charge).view(torch.int32).to(torch.int64)]).cpu().numpy()      # the one device-to-host copy
-        spectrum = packed[:S * H.PXD_BINS].reshape(S, H.PXD_BINS).copy()
-        n = (packed.size - S * H.PXD_BINS) // 2
-        hits = packed[S * H.PXD_BINS:S * H.PXD_BINS + n].reshape(-1, S)
-        charge = packed[S * H.PXD_BINS + n:].astype(np.int32).view(np.float32).reshape(-1, S)
         occupancy = (hits.astype(np.float64) / px).mean(0)
         has = hits > 0
         per = np.where(has, charge.astype(np.float64) / np.maximum(hits, 1), 0.0)
@@ -121,7 +188,7 @@ class PXDStatistics:
         b = (hits.reshape(-1) * 10000) // px
         occ_hist = np.bincount(b[b < PXD_OCC_BINS], minlength=PXD_OCC_BINS).astype(np.int64)
         return dict(spectrum=spectrum, occupancy=occupancy, mean_charge=mean_charge, occ_hist=occ_hist,
-                    occ_overflow=int((b >= PXD_OCC_BINS).sum()), n_events=int(hits.shape[0]), hits=hits.copy(), charge=charge.copy())
+                    occ_overflow=int((b >= PXD_OCC_BINS).sum()), n_events=int(hits.shape[0]), hits=hits, charge=charge)
 
 
 def pxd_distance(real, fake):
@@ -141,17 +208,18 @@ def pxd_distance(real, fake):
 PXD_DIGITS_FRACTION = 16    # default capacity of pxd_digits: one digit per 16 pixels (6.25 %; PXD background sits near 1 %)
 
 
-class PXDDigits:
+class PXDDigits(_PXDProduct):
     """Device-side result of ``pxd_digits``: ``index`` int32 ``[capacity]`` (flat position ``n*H*W + r*W + c``, ascending), ``charge``
     uint8 ``[capacity]``, ``counts`` int32 ``[N]``, ``total`` int32 ``[1]`` -- only the first ``min(total, capacity)`` digits are
     written.  ``start_copy`` enqueues the device-to-host copies, ``cpu()`` / ``unpack()`` wait for them (one wait)."""
+    _again = lambda self, capacity: pxd_digits(self.images, self.threshold, capacity, self.n_sensors)
 
     def __init__(self, images, threshold, capacity, n_sensors, header, index, charge):
         self.images, self.threshold, self.capacity, self.n_sensors = images, threshold, capacity, n_sensors
-        self.shape = tuple(images.shape)
-        self.header, self.index, self.charge = header, index, charge
-        self.counts, self.total = header[:self.shape[0]], header[self.shape[0]:]
-        self._host = None
+        self.shape, self.index, self.charge, self._host = tuple(images.shape), index, charge, None
+        self._set_header(header)
+
+    copied = property(lambda self: self._host[3] if self._host else 0, doc="Digits covered by the last ``start_copy`` (0 before the first).")
 
     def start_copy(self, expect=None, buffers=None):
         """Enqueue the copy of the header (``counts``, ``total``) and of the first ``expect`` digits (default: ``capacity``) into
@@ -185,10 +253,8 @@ class PXDDigits:
         N = self.shape[0]
         counts, total = hdr[:N].numpy().copy(), int(hdr[N])
         if total > self.capacity:
-            full = pxd_digits(self.images, self.threshold, capacity=total, n_sensors=self.n_sensors)
-            self.capacity, self.header, self.index, self.charge = total, full.header, full.index, full.charge
-            self.counts, self.total = full.counts, full.total
-            return self.index.cpu().numpy(), self.charge.cpu().numpy(), counts
+            self._grow(total)
+            m = 0                       # of the new arrays nothing is copied yet
         index, charge = idx[:min(m, total)].numpy().copy(), chg[:min(m, total)].numpy().copy()
         if total > m:
             index = np.concatenate([index, self.index[m:total].cpu().numpy()])
@@ -232,57 +298,45 @@ def pxd_digits(images, threshold=0.0, capacity=None, n_sensors=40):
     capacity = max(1024, N * Hh * Ww // PXD_DIGITS_FRACTION) if capacity is None else int(capacity)
     if capacity < 0:
         raise ValueError("pxd_digits: capacity is negative")
-    header = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    header, counts, total = _header(N, dev)
     index = torch.empty(capacity, dtype=torch.int32, device=dev)
     charge = torch.empty(capacity, dtype=torch.uint8, device=dev)
     scratch = torch.empty(H.lib().ieagan_pxd_digits_scratch(N, Hh, Ww), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         H.call("ieagan_pxd_digits", x.data_ptr(), int(x.dtype == torch.uint8), N, Hh, Ww, float(threshold), capacity,
-               *_ptrs(capacity, index, charge), header.data_ptr(), header.data_ptr() + 4 * N, scratch.data_ptr(), H.stream())
+               *_ptrs(capacity, index, charge), counts, total, scratch.data_ptr(), H.stream())
     return PXDDigits(x, float(threshold), capacity, int(n_sensors), header, index, charge)
 
 
 # ---------------------------------------------------------------------------------------------------------
 # detector-level validation, cluster level: connected components of the digits and their spectra (csrc/pxd_clusters.hip)
 # ---------------------------------------------------------------------------------------------------------
-class PXDClusters:
+class PXDClusters(_PXDProduct):
     """Device-side result of ``pxd_clusters``: the ``PXDDigits`` it was built from (``digits``), ``label`` int32 ``[capacity]`` (cluster
     number of digit k) and the cluster table ``first`` / ``size`` / ``charge`` / ``size_u`` / ``size_v`` int32 and ``seed`` uint8, all
     ``[capacity]`` (a batch has at most as many clusters as digits), ``counts`` int32 ``[N]`` (clusters per image), ``total`` int32
     ``[1]``.  Only the first ``min(digits.total, capacity)`` labels and the first ``total`` table rows are written."""
+    TABLE = ("first", "size", "charge", "seed", "size_u", "size_v")
+    _again = lambda self, capacity: pxd_clusters(self.images, self.threshold, capacity, self.n_sensors)
 
     def __init__(self, digits, label, first, size, charge, seed, size_u, size_v, header):
-        self.digits, self.capacity, self.n_sensors, self.shape = digits, digits.capacity, digits.n_sensors, digits.shape
-        self.label, self.first, self.size, self.charge, self.seed, self.size_u, self.size_v = label, first, size, charge, seed, size_u, size_v
-        self.header = header
-        self.counts, self.total = header[:self.shape[0]], header[self.shape[0]:]
+        self.digits, self.label = digits, label
+        self.first, self.size, self.charge, self.seed, self.size_u, self.size_v = first, size, charge, seed, size_u, size_v
+        self._set_header(header, digits)
 
     def cpu(self):
-        """One read-back (every array packed into one device tensor, one copy, one wait) -> dict of NumPy arrays trimmed to the true
-        totals: per digit ``index``, ``digit_charge``, ``label``; per cluster ``first``, ``size``, ``charge``, ``seed``, ``size_u``,
-        ``size_v``, ``sensor`` (``first // (H*W) % n_sensors``), ``event``; ``counts [N]``, ``digit_counts [N]``.  Never truncated: when
-        the digit total exceeds the capacity, digits and clusters are run again with ``capacity = total`` (a second read-back, on that
-        path only)."""
+        """One read-back (``pxd_read_back``: one copy, one wait) -> dict of NumPy arrays trimmed to the true totals: per digit ``index``,
+        ``digit_charge``, ``label``; per cluster ``first``, ``size``, ``charge``, ``seed``, ``size_u``, ``size_v``, ``sensor``
+        (``first // (H*W) % n_sensors``), ``event``; ``counts [N]``, ``digit_counts [N]``.  Never truncated (``_host_columns``)."""
         N, Hh, Ww = self.shape
-        d = self.digits
-        i32 = lambda t: t.to(torch.int32)
-        packed = torch.cat([d.header, self.header, d.index, self.label, self.first, self.size, self.charge, self.size_u, self.size_v,
-                            i32(d.charge), i32(self.seed)]).cpu().numpy()
-        dcounts, dtotal = packed[:N].copy(), int(packed[N])
-        counts, total = packed[N + 1:2 * N + 1].copy(), int(packed[2 * N + 1])
-        if dtotal > self.capacity:
-            full = pxd_clusters(d.images, d.threshold, capacity=dtotal, n_sensors=self.n_sensors)
-            for k in ("digits", "capacity", "label", "first", "size", "charge", "seed", "size_u", "size_v", "header", "counts", "total"):
-                setattr(self, k, getattr(full, k))
-            return full.cpu()
-        C = self.capacity
-        col = lambda k, m: packed[2 * N + 2 + k * C:2 * N + 2 + k * C + m].copy()
-        first = col(2, total)
-        image = first // np.int32(Hh * Ww)
-        return dict(index=col(0, dtotal), label=col(1, dtotal), first=first, size=col(3, total), charge=col(4, total), size_u=col(5, total),
-                    size_v=col(6, total), digit_charge=col(7, dtotal).astype(np.uint8), seed=col(8, total).astype(np.uint8),
-                    sensor=(image % self.n_sensors).astype(np.int32), event=(image // self.n_sensors).astype(np.int32), counts=counts,
-                    digit_counts=dcounts)
+        host = self._host_columns(lambda: dict(digit_header=self.digits.header, header=self.header, index=self.digits.index,
+                                               digit_charge=self.digits.charge, label=self.label, **{k: getattr(self, k) for k in self.TABLE}))
+        dtotal, total = int(host["digit_header"][N]), int(host["header"][N])
+        out = {k: host[k][:dtotal].copy() for k in ("index", "label", "digit_charge")}
+        out.update((k, host[k][:total].copy()) for k in self.TABLE)
+        image = out["first"] // np.int32(Hh * Ww)
+        return dict(out, sensor=(image % self.n_sensors).astype(np.int32), event=(image // self.n_sensors).astype(np.int32),
+                    counts=host["header"][:N].copy(), digit_counts=host["digit_header"][:N].copy())
 
 
 def pxd_clusters(images_or_digits, threshold=0.0, capacity=None, n_sensors=40):
@@ -304,41 +358,27 @@ def pxd_clusters(images_or_digits, threshold=0.0, capacity=None, n_sensors=40):
     i32 = lambda: torch.empty(C, dtype=torch.int32, device=dev)
     label, first, size, charge, size_u, size_v = i32(), i32(), i32(), i32(), i32(), i32()
     seed = torch.empty(C, dtype=torch.uint8, device=dev)
-    header = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    header, counts, total = _header(N, dev)
     scratch = torch.empty(H.lib().ieagan_pxd_clusters_scratch(N, Hh, Ww, C), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         H.call("ieagan_pxd_clusters", *_ptrs(C, d.index, d.charge), d.total.data_ptr(), N, Hh, Ww, C,
-               *_ptrs(C, label, first, size, charge, seed, size_u, size_v), header.data_ptr(), header.data_ptr() + 4 * N, scratch.data_ptr(),
-               H.stream())
+               *_ptrs(C, label, first, size, charge, seed, size_u, size_v), counts, total, scratch.data_ptr(), H.stream())
     return PXDClusters(d, label, first, size, charge, seed, size_u, size_v, header)
 
 
-class PXDClusterStatistics:
+class PXDClusterStatistics(_PXDAccumulator):
     """Accumulator of per-sensor cluster spectra over batches of sensor images in detector units (``[N, H, W]`` fp32 or uint8, image ``n``
     is sensor ``n % n_sensors``), beside ``PXDStatistics``: ``update`` runs digits -> clusters -> ``ieagan_pxd_cluster_stats`` on the
     current stream and neither synchronises nor copies; ``result()`` does the single read-back.  Counters are exact int64.
     ``capacity`` (digits per update) defaults to that of ``pxd_digits``; an update whose digit total exceeds it is counted on the device
-    and makes ``result()`` raise: a truncated event is never reported."""
+    and makes ``result()`` raise: a truncated event is never reported.  ``update`` also takes the ``PXDClusters`` of the batch and then
+    launches the statistics kernel alone.  ``tables``: int64 ``[S * 640 + 1]`` on the device, the spectra, then the overflow counter."""
 
-    def __init__(self, n_sensors=40, threshold=7.0, capacity=None, device=None):
-        self.n_sensors, self.threshold = int(n_sensors), float(threshold)
-        self.capacity = None if capacity is None else int(capacity)
-        self.device = torch.device(device) if device is not None else None
-        self.reset()
-
-    def reset(self):
-        self.tables = None              # int64 [S * 640 + 1] on the device: the spectra, then the overflow counter
-        self.clusters, self.shape = [], None
-
-    def update(self, images):
-        x = _sensor_images(images, self.n_sensors, "pxd_digits", self.device)       # a wrong dtype or rank is reported as by pxd_digits
-        self.device = self.device or x.device
-        if self.shape not in (None, tuple(x.shape[1:])):
-            raise ValueError(f"PXDClusterStatistics.update: image size {tuple(x.shape[1:])} differs from the accumulated {self.shape}")
-        self.shape = tuple(x.shape[1:])
-        c = pxd_clusters(x, self.threshold, self.capacity, self.n_sensors)
-        N, Hh, Ww = c.shape
-        S = self.n_sensors
+    def update(self, images_or_clusters):
+        c = self._input(images_or_clusters, "pxd_digits", PXDClusters)      # a wrong dtype or rank is reported as by pxd_digits
+        if not isinstance(c, PXDClusters):
+            c = pxd_clusters(c, self.threshold, self.capacity, self.n_sensors)
+        (N, Hh, Ww), S = c.shape, self.n_sensors
         if self.tables is None:
             self.tables = torch.zeros(S * H.PXD_CLUSTER_BINS + 1, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
@@ -352,20 +392,9 @@ class PXDClusterStatistics:
         """NumPy tables: int64 ``size_spectrum [S, 64]`` (bin ``min(size, 64) - 1``), ``charge_spectrum [S, 256]`` (bin
         ``min(charge >> 3, 255)``, 8 ADU a bin), ``seed_spectrum [S, 256]``, ``size_u_spectrum`` / ``size_v_spectrum [S, 32]`` (bin
         ``min(s, 32) - 1``), ``clusters`` int32 ``[events, S]`` (clusters per image) and ``n_events``.  Raises when an update overflowed."""
-        if not self.clusters:
-            raise RuntimeError("PXDClusterStatistics.result() before any update()")
-        S, B = self.n_sensors, H.PXD_CLUSTER_BINS
-        packed = torch.cat([self.tables, torch.cat(self.clusters).to(torch.int64)]).cpu().numpy()      # the one device-to-host copy
-        overflow = int(packed[S * B])
-        if overflow != 0:
-            raise RuntimeError(f"PXDClusterStatistics: {overflow} update(s) held more digits than the capacity"
-                               f"{'' if self.capacity is None else ' of %d' % self.capacity}, their clusters are truncated: "
-                               "pass a larger capacity= to PXDClusterStatistics")
-        rows = packed[:S * B].reshape(S, B)
-        out = {k: rows[:, a:a + n].copy() for k, (a, n) in H.PXD_CLUSTER_COLUMNS.items()}
-        out["clusters"] = packed[S * B + 1:].astype(np.int32).reshape(-1, S)
-        out["n_events"] = int(out["clusters"].shape[0])
-        return out
+        table, per_image = self._host_tables()
+        rows = table.reshape(self.n_sensors, H.PXD_CLUSTER_BINS)
+        return dict({k: rows[:, a:a + n].copy() for k, (a, n) in H.PXD_CLUSTER_COLUMNS.items()}, **per_image)
 
 
 def pxd_cluster_distance(real, fake):
@@ -390,45 +419,32 @@ def _check_cuts(who, seed_cut, charge_cut):
     return seed_cut, charge_cut
 
 
-class PXDClusterPositions:
+class PXDClusterPositions(_PXDProduct):
     """Device-side result of ``pxd_cluster_positions``: the ``PXDClusters`` it came from (``clusters``), the moments ``mu`` / ``mv`` int64
     ``[capacity]`` of every cluster (row j of the table: sum of charge x row, charge x column), and for the clusters that pass the cuts, in
     cluster order: ``cluster`` int32 (row of the table), ``u`` / ``v`` fp32 (charge-weighted row / column in cell units, the centre of cell
     ``r`` is ``r``), all ``[capacity]``; ``counts`` int32 ``[N]`` (accepted clusters per image), ``total`` int32 ``[1]``.  Only the first
     ``clusters.total`` moments and the first ``total`` rows of ``cluster`` / ``u`` / ``v`` are written."""
+    _again = lambda self, capacity: pxd_cluster_positions(self.images, self.threshold, self.seed_cut, self.charge_cut, capacity, self.n_sensors)
 
     def __init__(self, clusters, seed_cut, charge_cut, mu, mv, cluster, u, v, header):
-        self.clusters, self.capacity, self.n_sensors, self.shape = clusters, clusters.capacity, clusters.n_sensors, clusters.shape
-        self.seed_cut, self.charge_cut = seed_cut, charge_cut
-        self.mu, self.mv, self.cluster, self.u, self.v, self.header = mu, mv, cluster, u, v, header
-        self.counts, self.total = header[:self.shape[0]], header[self.shape[0]:]
+        self.clusters, self.seed_cut, self.charge_cut = clusters, seed_cut, charge_cut
+        self.mu, self.mv, self.cluster, self.u, self.v = mu, mv, cluster, u, v
+        self._set_header(header, clusters)
 
     def cpu(self):
-        """One read-back (every array packed into one device tensor, one copy, one wait) -> dict of NumPy arrays trimmed to the true
-        total, one entry per accepted cluster: ``cluster``, ``u``, ``v``, ``mu``, ``mv`` and, gathered through ``cluster``, ``sensor``,
-        ``event``, ``size``, ``charge``, ``seed``, ``size_u``, ``size_v``; plus ``counts [N]``.  Never truncated: when the digit total
-        exceeds the capacity, everything is run again with ``capacity = total`` (a second read-back, on that path only)."""
+        """One read-back (``pxd_read_back``: one copy, one wait) -> dict of NumPy arrays trimmed to the true total, one entry per accepted
+        cluster: ``cluster``, ``u``, ``v``, ``mu``, ``mv`` and, gathered through ``cluster``, ``sensor``, ``event``, ``size``, ``charge``,
+        ``seed``, ``size_u``, ``size_v``; plus ``counts [N]``.  Never truncated (``_host_columns``)."""
         N, Hh, Ww = self.shape
-        c = self.clusters
-        d = c.digits
-        packed = torch.cat([d.header, c.header, self.header, self.cluster, self.u.view(torch.int32), self.v.view(torch.int32), c.first, c.size,
-                            c.charge, c.size_u, c.size_v, c.seed.to(torch.int32), self.mu.view(torch.int32), self.mv.view(torch.int32)]).cpu().numpy()
-        dtotal = int(packed[N])
-        counts, total = packed[2 * N + 2:3 * N + 2].copy(), int(packed[3 * N + 2])
-        if dtotal > self.capacity:
-            full = pxd_cluster_positions(d.images, d.threshold, self.seed_cut, self.charge_cut, capacity=dtotal, n_sensors=self.n_sensors)
-            for k in ("clusters", "capacity", "mu", "mv", "cluster", "u", "v", "header", "counts", "total"):
-                setattr(self, k, getattr(full, k))
-            return full.cpu()
-        C = self.capacity
-        col = lambda k: packed[3 * N + 3 + k * C:3 * N + 3 + (k + 1) * C]
-        wide = lambda k: packed[3 * N + 3 + k * C:3 * N + 3 + (k + 2) * C].view(np.int64)
-        cluster = col(0)[:total].copy()
-        image = col(3)[cluster] // np.int32(Hh * Ww)
-        return dict(cluster=cluster, u=col(1)[:total].view(np.float32).copy(), v=col(2)[:total].view(np.float32).copy(),
-                    mu=wide(9)[cluster], mv=wide(11)[cluster], sensor=(image % self.n_sensors).astype(np.int32),
-                    event=(image // self.n_sensors).astype(np.int32), size=col(4)[cluster], charge=col(5)[cluster], size_u=col(6)[cluster],
-                    size_v=col(7)[cluster], seed=col(8)[cluster].astype(np.uint8), counts=counts)
+        host = self._host_columns(lambda: dict(digit_header=self.clusters.digits.header, header=self.header, cluster=self.cluster, u=self.u, v=self.v,
+                                               mu=self.mu, mv=self.mv, **{k: getattr(self.clusters, k) for k in PXDClusters.TABLE}))
+        total = int(host["header"][N])
+        cluster = host["cluster"][:total].copy()
+        image = host["first"][cluster] // np.int32(Hh * Ww)
+        return dict({k: host[k][:total].copy() for k in ("u", "v")}, cluster=cluster, sensor=(image % self.n_sensors).astype(np.int32),
+                    event=(image // self.n_sensors).astype(np.int32), counts=host["header"][:N].copy(),
+                    **{k: host[k][cluster] for k in ("mu", "mv", "size", "charge", "seed", "size_u", "size_v")})
 
 
 def pxd_cluster_positions(images_or_clusters, threshold=0.0, seed_cut=0, charge_cut=0, capacity=None, n_sensors=40):
@@ -451,43 +467,34 @@ def pxd_cluster_positions(images_or_clusters, threshold=0.0, seed_cut=0, charge_
     mu, mv = (torch.empty(C, dtype=torch.int64, device=dev) for _ in range(2))
     cluster = torch.empty(C, dtype=torch.int32, device=dev)
     u, v = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
-    header = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    header, counts, total = _header(N, dev)
     scratch = torch.empty(H.lib().ieagan_pxd_cluster_positions_scratch(N, Hh, Ww, C), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         H.call("ieagan_pxd_cluster_positions", *_ptrs(C, d.index, d.charge, c.label), d.total.data_ptr(), *_ptrs(C, c.first, c.charge, c.seed),
-               c.total.data_ptr(), N, Hh, Ww, C, seed_cut, charge_cut, *_ptrs(C, mu, mv, cluster, u, v), header.data_ptr(),
-               header.data_ptr() + 4 * N, scratch.data_ptr(), H.stream())
+               c.total.data_ptr(), N, Hh, Ww, C, seed_cut, charge_cut, *_ptrs(C, mu, mv, cluster, u, v), counts, total, scratch.data_ptr(),
+               H.stream())
     return PXDClusterPositions(c, seed_cut, charge_cut, mu, mv, cluster, u, v, header)
 
 
-class PXDClusterMaps:
+class PXDClusterMaps(_PXDAccumulator):
     """Accumulator of per-sensor position maps of the reconstructed clusters over batches of sensor images in detector units (``[N, H, W]``
     fp32 or uint8, image ``n`` is sensor ``n % n_sensors``), beside ``PXDClusterStatistics``: where on a sensor the clusters that pass the
     cuts lie, on a fixed grid of 25 x 48 bins over the image.  ``update`` runs digits -> clusters -> positions ->
     ``ieagan_pxd_cluster_maps`` on the current stream and neither synchronises nor copies; ``result()`` does the single read-back.
     Counters are exact int64; the bin of a cluster is decided in integers.  ``capacity`` (digits per update) defaults to that of
-    ``pxd_digits``; an update whose digit total exceeds it is counted on the device and makes ``result()`` raise."""
+    ``pxd_digits``; an update whose digit total exceeds it is counted on the device and makes ``result()`` raise.  ``update`` also takes
+    the ``PXDClusters`` of the batch (positions -> maps are launched) or its ``PXDClusterPositions`` (the maps kernel alone).  ``tables``:
+    int64 ``[2 * S * 25 * 48 + 1]`` on the device, count map, charge map, then the overflow counter."""
 
     def __init__(self, n_sensors=40, threshold=7.0, seed_cut=0, charge_cut=0, capacity=None, device=None):
-        self.n_sensors, self.threshold = int(n_sensors), float(threshold)
         self.seed_cut, self.charge_cut = _check_cuts("PXDClusterMaps", seed_cut, charge_cut)
-        self.capacity = None if capacity is None else int(capacity)
-        self.device = torch.device(device) if device is not None else None
-        self.reset()
+        super().__init__(n_sensors, threshold, capacity, device)
 
-    def reset(self):
-        self.tables = None              # int64 [2 * S * 25 * 48 + 1] on the device: count map, charge map, then the overflow counter
-        self.clusters, self.shape = [], None
-
-    def update(self, images):
-        x = _sensor_images(images, self.n_sensors, "pxd_digits", self.device)       # a wrong dtype or rank is reported as by pxd_digits
-        self.device = self.device or x.device
-        if self.shape not in (None, tuple(x.shape[1:])):
-            raise ValueError(f"PXDClusterMaps.update: image size {tuple(x.shape[1:])} differs from the accumulated {self.shape}")
-        self.shape = tuple(x.shape[1:])
-        p = pxd_cluster_positions(x, self.threshold, self.seed_cut, self.charge_cut, self.capacity, self.n_sensors)
-        c = p.clusters
-        N, Hh, Ww = p.shape
+    def update(self, images_or_product):
+        p = self._input(images_or_product, "pxd_digits", PXDClusters, PXDClusterPositions)      # a wrong dtype or rank is reported as by pxd_digits
+        if not isinstance(p, PXDClusterPositions):
+            p = pxd_cluster_positions(p, self.threshold, self.seed_cut, self.charge_cut, self.capacity, self.n_sensors)
+        c, (N, Hh, Ww) = p.clusters, p.shape
         S, B = self.n_sensors, H.PXD_MAP_U * H.PXD_MAP_V
         if self.tables is None:
             self.tables = torch.zeros(2 * S * B + 1, dtype=torch.int64, device=self.device)
@@ -503,28 +510,10 @@ class PXDClusterMaps:
         ``(floor(u / H * 25), floor(v / W * 48))``), ``u_profile [S, 25]`` and ``v_profile [S, 48]`` (sums of ``count_map`` over the other
         axis), ``clusters`` int32 ``[events, S]`` (accepted clusters per image), ``n_events`` and ``shape`` (the image size ``(H, W)``,
         which gives the bins their width in pixels).  Raises when an update overflowed."""
-        if not self.clusters:
-            raise RuntimeError("PXDClusterMaps.result() before any update()")
-        S, U, V = self.n_sensors, H.PXD_MAP_U, H.PXD_MAP_V
-        packed = torch.cat([self.tables, torch.cat(self.clusters).to(torch.int64)]).cpu().numpy()      # the one device-to-host copy
-        overflow = int(packed[2 * S * U * V])
-        if overflow != 0:
-            raise RuntimeError(f"PXDClusterMaps: {overflow} update(s) held more digits than the capacity"
-                               f"{'' if self.capacity is None else ' of %d' % self.capacity}, their clusters are truncated: "
-                               "pass a larger capacity= to PXDClusterMaps")
-        count_map = packed[:S * U * V].reshape(S, U, V).copy()
-        clusters = packed[2 * S * U * V + 1:].astype(np.int32).reshape(-1, S)
-        return dict(count_map=count_map, charge_map=packed[S * U * V:2 * S * U * V].reshape(S, U, V).copy(), u_profile=count_map.sum(2),
-                    v_profile=count_map.sum(1), clusters=clusters, n_events=int(clusters.shape[0]), shape=self.shape)
-
-
-def pxd_maps_accumulator(maps, **kw):
-    """The ``maps=`` keyword of ``train_fns.generated_statistics`` / ``validate.file_statistics``: None for False, else a ``PXDClusterMaps(**kw)``
-    without cuts (True) or with the cuts ``(seed_cut, charge_cut)``."""
-    if maps is False or maps is None:
-        return None
-    seed_cut, charge_cut = (0, 0) if maps is True else maps
-    return PXDClusterMaps(seed_cut=seed_cut, charge_cut=charge_cut, **kw)
+        table, per_image = self._host_tables()
+        count_map, charge_map = table.reshape(2, self.n_sensors, H.PXD_MAP_U, H.PXD_MAP_V)
+        return dict(count_map=count_map, charge_map=charge_map, u_profile=count_map.sum(2), v_profile=count_map.sum(1), **per_image,
+                    shape=self.shape)
 
 
 def pxd_map_distance(real, fake):
@@ -547,11 +536,67 @@ def pxd_map_distance(real, fake):
     return out
 
 
+class PXDValidation:
+    """The accumulators of one side of a validation, fed together: ``stats`` (a ``PXDStatistics``), ``clusters`` (a ``PXDClusterStatistics``
+    with ``clusters=True``, else None) and ``maps`` (a ``PXDClusterMaps`` without cuts with ``maps=True``, with the cuts of ``maps=(seed_cut,
+    charge_cut)``, else None); ``n_sensors``, ``threshold``, ``device`` and, where there is one, ``capacity`` go to each.  ``update`` runs the
+    chain once -- digits, clusters, positions -- and hands each accumulator the product before it; like the parts it neither synchronises
+    nor copies."""
+
+    def __init__(self, clusters=False, maps=False, capacity=None, **kw):
+        self.capacity, self.stats = capacity, PXDStatistics(**kw)
+        self.clusters = PXDClusterStatistics(capacity=capacity, **kw) if clusters else None
+        seed_cut, charge_cut = maps if isinstance(maps, (tuple, list)) else (0, 0)
+        self.maps = PXDClusterMaps(seed_cut=seed_cut, charge_cut=charge_cut, capacity=capacity, **kw) if maps not in (False, None) else None
+
+    def update(self, images):
+        x = _sensor_images(images, self.stats.n_sensors, "PXDValidation.update", self.stats.device)
+        self.stats.update(x)
+        if self.clusters is not None or self.maps is not None:
+            c = pxd_clusters(x, self.stats.threshold, self.capacity, self.stats.n_sensors)
+            for acc in filter(None, (self.clusters, self.maps)):
+                acc.update(c)
+
+    def result(self):
+        """``{"stats": ..., "clusters": ..., "maps": ...}``: the ``result()`` of every accumulator that is on."""
+        return {part: getattr(self, part).result() for part, _, _ in _PARTS if getattr(self, part) is not None}
+
+
+# the parts of a PXDValidation.result(): name, distance function, and the keys that are no table of their own beside the statistics'
+_PARTS = (("stats", pxd_distance, ()), ("clusters", pxd_cluster_distance, ("n_events",)), ("maps", pxd_map_distance, ("n_events", "shape")))
+
+
+def pxd_validation_distance(real, fake):
+    """``pxd_distance``, ``pxd_cluster_distance`` and ``pxd_map_distance`` of the parts both ``PXDValidation.result()`` have, in one dict."""
+    return {k: v for part, distance, _ in _PARTS if part in real and part in fake for k, v in distance(real[part], fake[part]).items()}
+
+
+def pxd_validation_tables(**sides):
+    """``pxd_validation_tables(real=r, fake=f)``: every table of each side's ``PXDValidation.result()`` as ``<side>_<name>``, part by part;
+    the per-image ``clusters`` of the maps are ``<side>_accepted_clusters``, beside the cluster statistics' ``<side>_clusters``."""
+    return {f"{side}_{'accepted_clusters' if (part, k) == ('maps', 'clusters') else k}": np.asarray(v) for part, _, skip in _PARTS
+            for side, res in sides.items() for k, v in res.get(part, {}).items() if k not in skip}
+
+
+# the columns of the event file of ``produce.py`` / ``pack_events.py`` and their types: the events, then four columns of the digits
+EVENT_COLUMNS = dict(event_offsets=np.int64, sensor=np.uint8, ucell=np.uint8, vcell=np.uint16, charge=np.uint8)
+_digit_columns = lambda *columns: dict(zip(list(EVENT_COLUMNS)[1:], map(np.asarray, columns)))
+
+
+def _load_event_file(path, columns=tuple(EVENT_COLUMNS)):
+    """The arrays ``columns`` of an event file, after the check that it is one."""
+    with np.load(path) as t:
+        missing = [k for k in EVENT_COLUMNS if k not in t.files]
+        if missing:
+            raise ValueError(f"PXDEventStore: {path} is no event file of write_digits, it lacks {missing}")
+        return [t[k] for k in columns]
+
+
 def write_digits(path, event_offsets, sensor, ucell, vcell, charge):
     """The event file of ``produce.py`` (``.npz``): ``event_offsets`` int64 ``[events + 1]`` (the digits of event ``e`` are
     ``[event_offsets[e], event_offsets[e + 1])``), ``sensor`` uint8, ``ucell`` uint8, ``vcell`` uint16, ``charge`` uint8."""
     event_offsets = np.asarray(event_offsets, np.int64)
-    cols = dict(sensor=np.asarray(sensor), ucell=np.asarray(ucell), vcell=np.asarray(vcell), charge=np.asarray(charge))
+    cols = _digit_columns(sensor, ucell, vcell, charge)
     if event_offsets.ndim != 1 or event_offsets.size < 1 or event_offsets[0] != 0 or (np.diff(event_offsets) < 0).any():
         raise ValueError("write_digits: event_offsets must start at 0 and not decrease")
     for k, v in cols.items():
@@ -560,15 +605,13 @@ def write_digits(path, event_offsets, sensor, ucell, vcell, charge):
     if cols["sensor"].size and (cols["sensor"].max() > 255 or cols["ucell"].max() > 255 or cols["vcell"].max() > 65535):
         raise ValueError("write_digits: a sensor / ucell / vcell value does not fit the file's uint8 / uint8 / uint16 columns")
     with open(path, "wb") as fh:
-        np.savez(fh, event_offsets=event_offsets, sensor=cols["sensor"].astype(np.uint8), ucell=cols["ucell"].astype(np.uint8),
-                 vcell=cols["vcell"].astype(np.uint16), charge=cols["charge"].astype(np.uint8))
+        np.savez(fh, event_offsets=event_offsets, **{k: v.astype(EVENT_COLUMNS[k]) for k, v in cols.items()})
 
 
 def read_digits(path):
     """Yields the events of a ``produce.py`` file in the format ``create_g1.generate`` puts on its queue (create_g1.py:79, read by
     ``DigitCreator.event`` :105-106): ``((sensor, ucell, vcell) lists, charges list)``."""
-    with np.load(path) as t:
-        off, sensor, ucell, vcell, charge = (t[k] for k in ("event_offsets", "sensor", "ucell", "vcell", "charge"))
+    off, sensor, ucell, vcell, charge = _load_event_file(path)
     for e in range(off.size - 1):
         s = slice(int(off[e]), int(off[e + 1]))
         yield (sensor[s].tolist(), ucell[s].tolist(), vcell[s].tolist()), charge[s].tolist()
@@ -601,7 +644,7 @@ def event_columns(event_offsets, sensor, ucell, vcell, charge, shape=(250, 768),
     down = np.nonzero(np.diff(off) < 0)[0]
     if down.size:
         raise ValueError(f"{who}: event_offsets decreases at event {int(down[0])} ({off[down[0]]} -> {off[down[0] + 1]})")
-    cols = dict(sensor=np.asarray(sensor), ucell=np.asarray(ucell), vcell=np.asarray(vcell), charge=np.asarray(charge))
+    cols = _digit_columns(sensor, ucell, vcell, charge)
     for k, v in cols.items():
         if v.ndim != 1 or v.size != off[-1]:
             raise ValueError(f"{who}: {k} has {v.size} entries, event_offsets ends at {off[-1]}")
@@ -642,12 +685,7 @@ def select_events(event_offsets, events, *columns):
 def read_event_columns(path, shape=(250, 768), n_sensors=40, events=None):
     """The host half of ``PXDEventStore.from_file``: the file of ``write_digits`` -> checked ``(offsets, pos, charge)`` of ``event_columns``,
     of all events or of the subset ``events``."""
-    with np.load(path) as t:
-        missing = [k for k in ("event_offsets", "sensor", "ucell", "vcell", "charge") if k not in t.files]
-        if missing:
-            raise ValueError(f"PXDEventStore: {path} is no event file of write_digits, it lacks {missing}")
-        off, sensor, ucell, vcell, charge = (t[k] for k in ("event_offsets", "sensor", "ucell", "vcell", "charge"))
-    off, pos, charge = event_columns(off, sensor, ucell, vcell, charge, shape, n_sensors, who=f"PXDEventStore ({path})")
+    off, pos, charge = event_columns(*_load_event_file(path), shape, n_sensors, who=f"PXDEventStore ({path})")
     return (off, pos, charge) if events is None else select_events(off, events, pos, charge)
 
 
@@ -661,8 +699,7 @@ def split_positions(pos, shape=(250, 768)):
 
 def event_file_length(path):
     """Number of events in a file of ``write_digits`` (reads the offsets only)."""
-    with np.load(path) as t:
-        return int(t["event_offsets"].size - 1)
+    return int(_load_event_file(path, ("event_offsets",))[0].size - 1)
 
 
 class PXDEventStore:

@@ -101,18 +101,14 @@ def test(G, D, G_ema, state_dict, config, test_log):
 
 
 def generated_statistics(net, config, n_events, clusters=False, maps=False):
-    """``utils.PXDStatistics`` over ``n_events`` events generated by ``net`` (eval mode when ``G_eval_mode``, no_grad, export epilogue).
-    The latents and ``rdof`` come from a ``torch.Generator`` of its own seeded with ``config['seed']``: the global generators are not
-    touched; the ``.training`` flags are restored.  No host synchronisation.  ``clusters=True``: the same events also go through a
-    ``utils.PXDClusterStatistics`` and ``(statistics, cluster statistics)`` is returned.  ``maps=True`` or ``maps=(seed_cut, charge_cut)``
-    (ADU): a ``utils.PXDClusterMaps`` with these cuts is fed as well and appended to the returned tuple."""
+    """A ``utils.PXDValidation`` over ``n_events`` events generated by ``net`` (eval mode when ``G_eval_mode``, no_grad, export epilogue):
+    its ``.stats``, with ``clusters=True`` its ``.clusters`` and with ``maps=True`` or ``maps=(seed_cut, charge_cut)`` (ADU) its ``.maps``
+    are fed.  The latents and ``rdof`` come from a ``torch.Generator`` of its own seeded with ``config['seed']``: the global generators
+    are not touched; the ``.training`` flags are restored.  No host synchronisation."""
     dev = next(net.parameters()).device
     n = int(config["n_classes"])
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(int(config["seed"]))
-    stats = utils.PXDStatistics(n_sensors=n, threshold=float(config["val_threshold"]), device=dev)
-    cstats = utils.PXDClusterStatistics(n_sensors=n, threshold=float(config["val_threshold"]), device=dev) if clusters else None
-    mstats = utils.pxd_maps_accumulator(maps, n_sensors=n, threshold=float(config["val_threshold"]), device=dev)
+    gen = torch.Generator(device=dev).manual_seed(int(config["seed"]))
+    acc = utils.PXDValidation(clusters, maps, n_sensors=n, threshold=float(config["val_threshold"]), device=dev)
     y = torch.arange(n, dtype=torch.long, device=dev)
     was_training = net.training
     if config["G_eval_mode"]:
@@ -122,16 +118,10 @@ def generated_statistics(net, config, n_events, clusters=False, maps=False):
             for _ in range(n_events):
                 z = torch.randn(n, net.dim_z, generator=gen, device=dev)
                 rdof = torch.randn(n, net.rdof_dim, generator=gen, device=dev)
-                x = net(z, y, rdof=rdof, export=True)
-                stats.update(x)
-                if clusters:
-                    cstats.update(x)
-                if mstats is not None:
-                    mstats.update(x)
+                acc.update(net(z, y, rdof=rdof, export=True))
     finally:
         net.train(was_training)
-    extra = tuple(a for a in (cstats, mstats) if a is not None)
-    return (stats,) + extra if extra else stats
+    return acc
 
 
 def validate(G, G_ema, real_stats, state_dict, config, log=None):
@@ -148,7 +138,7 @@ def validate(G, G_ema, real_stats, state_dict, config, log=None):
     import os
     which, net = ("G_ema", G_ema) if (config["ema"] and config["use_ema"] and G_ema is not None) else ("G", G)
     real = real_stats.result() if isinstance(real_stats, utils.PXDStatistics) else real_stats
-    fake = generated_statistics(net, config, int(config["val_events"]))
+    fake = generated_statistics(net, config, int(config["val_events"])).stats
     rec = dict(itr=int(state_dict["itr"]), n_events=int(config["val_events"]), which=which, **utils.pxd_distance(real, fake.result()))
     line = json.dumps(rec) + "\n"
     if log is not None:

@@ -225,14 +225,14 @@ def test_file_statistics_over_a_store_equal_those_over_the_dense_events():
     cfg = dict(n_classes=S, val_threshold=7.0)
     a = validate.file_statistics(events, cfg, 4, DEV, clusters=True)
     b = validate.file_statistics(store, cfg, 4, DEV, clusters=True)
-    for dense_acc, store_acc in zip(a, b):
+    for dense_acc, store_acc in ((a.stats, b.stats), (a.clusters, b.clusters)):
         r, f = dense_acc.result(), store_acc.result()
         assert set(r) == set(f) and r["n_events"] == 4
         for k in r:
             assert np.array_equal(np.asarray(r[k]), np.asarray(f[k]), equal_nan=np.asarray(r[k]).dtype.kind == "f"), k
-    assert a[0].result()["hits"].sum() > 0 and a[1].result()["clusters"].sum() > 0
-    few = validate.file_statistics(store, cfg, 2, DEV)
-    assert few.result()["n_events"] == 2 and np.array_equal(few.result()["hits"], a[0].result()["hits"][:2])
+    assert a.stats.result()["hits"].sum() > 0 and a.clusters.result()["clusters"].sum() > 0
+    few = validate.file_statistics(store, cfg, 2, DEV).stats
+    assert few.result()["n_events"] == 2 and np.array_equal(few.result()["hits"], a.stats.result()["hits"][:2])
 
 
 def test_validate_tool_takes_a_digit_file_on_either_side(tmp_path):
