@@ -160,6 +160,8 @@ _SIGS = {
     "ieagan_pxd_cluster_positions": [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, l, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "ieagan_pxd_cluster_positions_scratch": [i, i, i, l],
     "ieagan_pxd_cluster_maps": [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, l, vp, vp, vp, vp],
+    "ieagan_pxd_hits": [vp] * 16 + [i, i, i, i, i, l, i] + [vp] * 12,
+    "ieagan_pxd_hits_scratch": [i, i, i, l],
     "ieagan_pxd_event_ingest": [vp, vp, vp, l, i, vp, i, i, i, i, i, vp, f, vp, vp],
     "ieagan_pxd_event_dense": [vp, vp, vp, l, i, vp, i, i, i, i, vp, vp],
     "ieagan_ortho_ksplit": [],

@@ -1,4 +1,4 @@
-// What the kernels over PXD sensor images share (pxd_stats.hip, pxd_digits.hip, pxd_clusters.hip, pxd_reco.hip, pxd_events.hip): the launch partition, the walk
+// What the kernels over PXD sensor images share (pxd_stats.hip, pxd_digits.hip, pxd_clusters.hip, pxd_reco.hip, pxd_hits.hip, pxd_events.hip): the launch partition, the walk
 // of a pixel range, the prefix sums, the row / column split and the launchers' argument checks.  Include after common.h.
 //
 // Launch partition: grid (P, N), workgroup (p, n) owns a contiguous pixel range of image n.
@@ -126,6 +126,31 @@ __device__ __forceinline__ int pxd_scan_slots(int* __restrict__ slots, int group
         __syncthreads();                    // wsum is rewritten by the next tile; the bases written above are visible to this workgroup
     }
     return carry;
+}
+
+// Runs of equal label in lane order (digits ascend in flat index, so the 64 digits of a wave's step fall into few runs).  `head`: this lane
+// is the first of its run; `end`: the lane behind its run's last.
+struct PxdRun {
+    bool head;
+    int end;
+};
+__device__ __forceinline__ PxdRun pxd_run(int lab, int lane) {
+    const int before = __shfl_up(lab, 1, 64);
+    const bool head = lane == 0 || before != lab;
+    const unsigned long long later = __ballot(head) & ~((2ull << lane) - 1ull);          // heads in the higher lanes
+    return {head, later ? __ffsll(later) - 1 : 64};
+}
+// Segmented reduction over the runs: a lane combines its own run from itself to the run's end, so the head lane of a run gets it all.
+template <typename T, typename Op> __device__ __forceinline__ T pxd_run_reduce(T x, int lane, int end, Op op) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_down(x, o, 64);
+        if (lane + o < end) x = op(x, y);
+    }
+    return x;
+}
+template <typename T> __device__ __forceinline__ T pxd_run_sum(T x, int lane, int end) {
+    return pxd_run_reduce(x, lane, end, [](T a, T b) { return a + b; });
 }
 
 __device__ __forceinline__ int cl_lower_bound(const int* __restrict__ a, int n, int v) {

@@ -76,20 +76,10 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_reco_moments_kernel(const int
             qr = q * (u64)r;
             qc = q * (u64)c;
         }
-        // runs of equal label in lane order: a lane sums its own run from itself to the run's end, so the first lane of a run gets it all
-        const int before = __shfl_up(lab, 1, 64);
-        const bool head = lane == 0 || before != lab;
-        const u64 later = __ballot(head) & ~((2ull << lane) - 1ull);          // heads in the higher lanes
-        const int end = later ? __ffsll(later) - 1 : 64;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u64 a = __shfl_down(qr, o, 64), b = __shfl_down(qc, o, 64);
-            if (lane + o < end) {
-                qr += a;
-                qc += b;
-            }
-        }
-        if (head && lab >= 0) {
+        const PxdRun run = pxd_run(lab, lane);
+        qr = pxd_run_sum(qr, lane, run.end);
+        qc = pxd_run_sum(qc, lane, run.end);
+        if (run.head && lab >= 0) {
             if (qr) atomicAdd(mu + lab, qr);
             if (qc) atomicAdd(mv + lab, qc);
         }

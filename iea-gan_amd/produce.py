@@ -2,7 +2,7 @@
 """Event production: the reference's ``Physics_Analysis/create_g1.py`` up to the digits, without basf2.
 
     produce.py --weights RUN/weights --events N --out FILE.npz [--events_per_batch E] [--use_ema] [--weight_name S] [--seed S]
-               [--threshold T] [--synthetic-weights]
+               [--threshold T] [--synthetic-weights] [--hits FILE [--seed_cut S --cluster_cut C --head_tail T --uniform_pitch U V]]
 
 Loads the checkpoint under ``--weights`` the way ``validate.py`` does (the ``weights`` directory of a run; ``--use_ema`` takes
 ``G_ema.pth``; ``--synthetic-weights`` takes a freshly initialised generator instead, for tests and measurements) and generates ``N``
@@ -19,7 +19,14 @@ rerun, never a truncation.
 uint16 (column), ``charge`` uint8, digits in ``nonzero()`` order inside an event; ``utils.read_digits`` yields the events in the format
 ``create_g1.generate`` puts on its queue.  ``<out>.json`` carries the checkpoint's sha256 and the arguments (create_g1.py:173-189).
 Writing the digits into a basf2 ``RootOutput`` file (create_g1.py:91-122) needs basf2 and ROOT and is out of scope: a ``DigitCreator``
-module fed from ``utils.read_digits`` is the bridge.  One JSON line with the rates is printed at the end.  The network geometry is
+module fed from ``utils.read_digits`` is the bridge.
+
+``--hits FILE`` also reconstructs every batch on the device, on the digits it already has (they are not computed twice): clusters, the cuts
+``--seed_cut`` / ``--cluster_cut`` (ADU), positions and ``utils.pxd_hits`` with ``--head_tail`` in the nominal geometry
+``utils.PXDGeometry.belle2`` (design values, not checked against basf2; it exists for 40 sensors of 250 x 768 cells only, any other
+configured geometry needs ``--uniform_pitch U V``, the cell size in um).  The hits of a batch are one more read-back; ``FILE`` is the hit
+file of ``utils.write_hits`` (local positions in mm from the sensor centre) and the record gains ``hits`` and ``hit_waits``.  Position errors,
+global coordinates and a basf2 writer are out of scope.  One JSON line with the rates is printed at the end.  The network geometry is
 given like in ``train.py``: ``--config config.json`` and / or ``--key value``.
 """
 from __future__ import annotations
@@ -80,16 +87,37 @@ def event_batches(G, cfg, n_events, per_batch, seed):
         G.train(was_training)
 
 
-def produce(G, cfg, n_events, per_batch, seed, threshold=0.0):
-    """Columns of the event file and a small record: ``(event_offsets, sensor, ucell, vcell, charge, rec)``."""
+def hit_geometry(cfg, uniform_pitch=None):
+    """The ``PXDGeometry`` of ``--hits`` for the configured sensors: ``belle2`` for 40 sensors of 250 x 768 cells, else ``uniform`` with the
+    cell size ``uniform_pitch = (u, v)`` in um; ``SystemExit`` when neither applies."""
+    n, shape = int(cfg["n_classes"]), (cfg["resolution"] - 6, cfg["resolution"] * cfg["H_base"])
+    if uniform_pitch is not None:
+        units = [2.0 * float(p) for p in uniform_pitch]         # the geometry unit is 0.5 um
+        if any(p != int(p) for p in units):
+            raise SystemExit(f"--uniform_pitch {uniform_pitch}: a pitch must be a multiple of 0.5 um")
+        try:
+            return utils.PXDGeometry.uniform(shape, int(units[0]), int(units[1]), n)
+        except ValueError as e:
+            raise SystemExit(f"--uniform_pitch {uniform_pitch}: {e}")
+    if shape != (250, 768) or n != 40:
+        raise SystemExit(f"--hits: the nominal PXD geometry is known for 40 sensors of 250 x 768 cells, not {n} of {shape[0]} x {shape[1]}: "
+                         "give the cell size with --uniform_pitch U V (um)")
+    return utils.PXDGeometry.belle2()
+
+
+def produce(G, cfg, n_events, per_batch, seed, threshold=0.0, hits=None):
+    """Columns of the event file and a small record: ``(event_offsets, sensor, ucell, vcell, charge, rec)``.  With ``hits =
+    dict(geometry=, seed_cut=, charge_cut=, head_tail=)`` every batch is also reconstructed (clusters -> positions -> ``utils.pxd_hits`` on
+    the batch's own digits) and a seventh element follows: the arguments of ``utils.write_hits`` as a dict."""
     n = int(cfg["n_classes"])
     h, w = cfg["resolution"] - 6, cfg["resolution"] * cfg["H_base"]
     capacity = max(1024, per_batch * n * h * w // utils.PXD_DIGITS_FRACTION)
     pinned = [(torch.empty(per_batch * n + 1, dtype=torch.int32, pin_memory=True), torch.empty(capacity, dtype=torch.int32, pin_memory=True),
                torch.empty(capacity, dtype=torch.uint8, pin_memory=True)) for _ in range(2)]
     found, per_event, stats = [], [], dict(waits=0, extra_copies=0, bytes_copied=0, last=0)
+    found_hits, hits_per_event = [], []
 
-    def finish(d):
+    def finish(d, hit):
         index, charge, counts = d.cpu()         # copies out of the pinned buffers, which the batch after next reuses
         stats["waits"] += 1
         stats["extra_copies"] += int(index.size > d.copied)
@@ -97,15 +125,23 @@ def produce(G, cfg, n_events, per_batch, seed, threshold=0.0):
         stats["last"] = index.size
         found.append((index, charge))
         per_event.append(counts.reshape(-1, n).sum(1))
+        if hit is not None:
+            host = hit.cpu()                    # the hits of the batch: one more read-back
+            found_hits.append(host)
+            hits_per_event.append(host["counts"].reshape(-1, n).sum(1))
 
     pending = None
     for k, x in enumerate(event_batches(G, cfg, n_events, per_batch, seed)):
         expect = capacity if not stats["last"] else min(capacity, stats["last"] + stats["last"] // 2 + 64)
         d = utils.pxd_digits(x, threshold=threshold, capacity=capacity, n_sensors=n).start_copy(expect, pinned[k % 2])
+        hit = None
+        if hits is not None:                    # enqueued behind the digit copies: the wait for the digits does not wait for the hits
+            p = utils.pxd_cluster_positions(utils.pxd_clusters(d), seed_cut=hits["seed_cut"], charge_cut=hits["charge_cut"])
+            hit = utils.pxd_hits(p, hits["geometry"], hits["head_tail"])
         if pending is not None:
-            finish(pending)             # batch k is already enqueued while the host waits for batch k - 1
-        pending = d
-    finish(pending)
+            finish(*pending)            # batch k is already enqueued while the host waits for batch k - 1
+        pending = (d, hit)
+    finish(*pending)
     offsets = np.concatenate([[0], np.cumsum(np.concatenate(per_event))]).astype(np.int64)
     # one split of every position at the end: sensor, row and column do not depend on the batch an image came in
     _, sensor, ucell, vcell, charge = utils.unpack_digits(np.concatenate([f[0] for f in found]), np.concatenate([f[1] for f in found]),
@@ -113,7 +149,13 @@ def produce(G, cfg, n_events, per_batch, seed, threshold=0.0):
     rec = dict(events=n_events, digits=int(offsets[-1]), host_waits=stats["waits"], extra_copies=stats["extra_copies"],
                bytes_copied_per_event=stats["bytes_copied"] / n_events,
                dense_bytes_per_event=4 * n * h * w)
-    return offsets, sensor, ucell, vcell, charge, rec
+    if hits is None:
+        return offsets, sensor, ucell, vcell, charge, rec
+    columns = {k: np.concatenate([f[k] for f in found_hits]) for k in list(utils.HIT_COLUMNS)[1:]}
+    columns.update(event_offsets=np.concatenate([[0], np.cumsum(np.concatenate(hits_per_event))]).astype(np.int64),
+                   unit_mm=hits["geometry"].unit_mm)
+    rec.update(hits=int(columns["event_offsets"][-1]), hit_waits=len(found_hits))
+    return offsets, sensor, ucell, vcell, charge, rec, columns
 
 
 def run(argv):
@@ -127,21 +169,38 @@ def run(argv):
     ap.add_argument("--weight_name", default=None, help="checkpoint suffix (e.g. copy1000)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--threshold", type=float, default=0.0, help="digit cut in ADU (0: every nonzero uint8 charge, 7: the evaluation cut)")
+    ap.add_argument("--hits", default=None, help="also reconstruct the events and write this hit file (.npz, utils.write_hits)")
+    ap.add_argument("--seed_cut", type=int, default=0, help="--hits: seed cut in ADU")
+    ap.add_argument("--cluster_cut", type=int, default=0, help="--hits: cluster-charge cut in ADU")
+    ap.add_argument("--head_tail", type=int, default=3, help="--hits: head-tail from this many cells on (0: never)")
+    ap.add_argument("--uniform_pitch", type=float, nargs=2, default=None, metavar=("U", "V"),
+                    help="--hits: one cell size in um instead of the nominal PXD geometry")
     args, rest = ap.parse_known_args(argv)
     cfg = train.parse(rest)
     if (args.weights is None) == (not args.synthetic_weights):
         raise SystemExit("give exactly one of --weights DIR and --synthetic-weights")
     if args.events <= 0 or args.events_per_batch <= 0:
         raise SystemExit("--events and --events_per_batch must be positive")
+    hits = None
+    if args.hits is not None:
+        if args.seed_cut < 0 or args.cluster_cut < 0 or (args.head_tail != 0 and args.head_tail < 3):
+            raise SystemExit("--seed_cut and --cluster_cut must not be negative, --head_tail is 0 or at least 3")
+        hits = dict(geometry=hit_geometry(cfg, args.uniform_pitch), seed_cut=args.seed_cut, charge_cut=args.cluster_cut, head_tail=args.head_tail)
     utils.H.require_gpu()
     G, digest = load_generator(cfg, args.weights, args.use_ema, args.weight_name, args.synthetic_weights, args.seed)
     with open(args.out + ".json", "w") as fh:
-        json.dump({"sha256(checkpoint)": digest, **vars(args)}, fh, indent=4, sort_keys=True)
+        side = {k: v for k, v in vars(args).items() if hits is not None or k not in ("hits", "seed_cut", "cluster_cut", "head_tail", "uniform_pitch")}
+        json.dump({"sha256(checkpoint)": digest, **side}, fh, indent=4, sort_keys=True)
     t0 = time.perf_counter()
-    offsets, sensor, ucell, vcell, charge, rec = produce(G, cfg, args.events, args.events_per_batch, args.seed, args.threshold)
+    offsets, sensor, ucell, vcell, charge, rec, *hit_columns = produce(G, cfg, args.events, args.events_per_batch, args.seed, args.threshold, hits)
     rec["seconds"] = time.perf_counter() - t0
     rec["events_per_s"] = args.events / rec["seconds"]
     utils.write_digits(args.out, offsets, sensor, ucell, vcell, charge)
+    if hits is not None:
+        try:
+            utils.write_hits(args.hits, **hit_columns[0])
+        except ValueError as e:                 # e.g. a cluster of more than 65535 digits: no detector event, the digit file stands
+            raise SystemExit(f"--hits: {e}; {args.out} is written, {args.hits} is not")
     print(json.dumps(rec))
     return rec
 

@@ -1,7 +1,7 @@
 """The PXD detector surface, this project's own (no counterpart in the reference's ``utils``): detector-level validation statistics
 (csrc/pxd_stats.hip), event production as sparse digits (csrc/pxd_digits.hip), clusters of the digits and their spectra
-(csrc/pxd_clusters.hip), cluster reconstruction -- cuts, charge-weighted positions, per-sensor position maps (csrc/pxd_reco.hip) --, the
-event file of ``produce.py`` and the store that keeps such a file's events on the device and expands them into the network input
+(csrc/pxd_clusters.hip), cluster reconstruction -- cuts, charge-weighted positions, per-sensor position maps (csrc/pxd_reco.hip) --, hits in the local
+frame of a sensor with a geometry given as data (csrc/pxd_hits.hip), the event and hit files of ``produce.py`` and the store that keeps such a file's events on the device and expands them into the network input
 (csrc/pxd_events.hip).  ``utils`` re-exports every name defined here."""
 from __future__ import annotations
 
@@ -615,6 +615,190 @@ def read_digits(path):
     for e in range(off.size - 1):
         s = slice(int(off[e]), int(off[e + 1]))
         yield (sensor[s].tolist(), ucell[s].tolist(), vcell[s].tolist()), charge[s].tolist()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# hits: positions of the accepted clusters in the local frame of their sensor, head-tail for wide clusters (csrc/pxd_hits.hip)
+# ---------------------------------------------------------------------------------------------------------
+class PXDGeometry:
+    """The cell pitches of ``K`` sensor types as data: ``u_pitch`` int ``[K, H]`` (rows), ``v_pitch`` int ``[K, W]`` (columns) in integer
+    geometry units of ``unit_mm`` mm (default 0.5 um, in which every nominal PXD pitch and half-pitch is an integer), and ``kind`` int ``[S]``,
+    the type of every sensor (default: 40 sensors of type 0, valid only when ``K == 1``).
+
+    Derived per type and axis: the doubled, centred cell centres ``x2[k] = 2 * sum(pitch[:k]) + pitch[k] - sum(pitch)`` -- twice the distance
+    of the centre of cell ``k`` from the sensor centre, an integer even for odd pitches.  ``u_x2``, ``u_pitch``, ``v_x2``, ``v_pitch`` and
+    ``kind`` are int32 NumPy arrays; ``tables(device)`` gives their device copies, uploaded once per device on first use.
+
+    ``ValueError`` for a pitch outside ``1 .. 4095``, a total length ``sum(pitch) >= 2**20`` units, a ``kind`` outside ``0 .. K-1`` and shapes
+    that disagree.  These bounds are what makes ``pxd_hits`` exact: ``|x2| < 2**20``, a cluster charge is below ``2**31`` (``H * W * 255 <
+    2**31``, checked by the launchers), so a moment ``sum q * x2`` stays below ``2**51``, the head-tail numerator ``(x2[lo] + x2[hi]) * D + 2 *
+    (q_tail * p[hi] - q_head * p[lo]) * (s - 2)`` below ``2**52 + 2**45`` and every product of the clamp comparison inside int64: numerator
+    and denominator of a position convert to float64 without rounding."""
+
+    def __init__(self, u_pitch, v_pitch, kind=None, unit_mm=5e-4):
+        u, v = np.asarray(u_pitch), np.asarray(v_pitch)
+        if u.ndim != 2 or v.ndim != 2 or u.shape[0] != v.shape[0] or 0 in u.shape + v.shape or u.dtype.kind not in "iu" or v.dtype.kind not in "iu":
+            raise ValueError(f"PXDGeometry: u_pitch {u.shape} {u.dtype} / v_pitch {v.shape} {v.dtype} are not integer arrays [K, H] and [K, W]")
+        u, v = u.astype(np.int64), v.astype(np.int64)
+        if kind is None and u.shape[0] != 1:
+            raise ValueError(f"PXDGeometry: {u.shape[0]} sensor types need a kind [S]")
+        kind = np.zeros(40, np.int64) if kind is None else np.asarray(kind)
+        if kind.ndim != 1 or kind.size == 0 or kind.dtype.kind not in "iu":
+            raise ValueError(f"PXDGeometry: kind {kind.shape} {kind.dtype} is not an integer array [S]")
+        for name, p in (("u_pitch", u), ("v_pitch", v)):
+            if p.min() < 1 or p.max() > 4095:
+                raise ValueError(f"PXDGeometry: {name} holds {int(p.min())} .. {int(p.max())}, outside 1 .. 4095")
+            if p.sum(1).max() >= 2 ** 20:
+                raise ValueError(f"PXDGeometry: a sensor is {int(p.sum(1).max())} units long along {name[0]}, not below 2**20")
+        if kind.min() < 0 or kind.max() >= u.shape[0]:
+            raise ValueError(f"PXDGeometry: kind holds {int(kind.min())} .. {int(kind.max())}, outside the {u.shape[0]} type(s)")
+        x2 = lambda p: (2 * (np.cumsum(p, 1) - p) + p - p.sum(1, keepdims=True)).astype(np.int32)
+        self.u_pitch, self.v_pitch, self.u_x2, self.v_x2 = u.astype(np.int32), v.astype(np.int32), x2(u), x2(v)
+        self.kind, self.unit_mm, self._device = kind.astype(np.int32), float(unit_mm), {}
+        self.K, self.H, self.W, self.S = u.shape[0], u.shape[1], v.shape[1], kind.size
+        self.u_length, self.v_length = u.sum(1), v.sum(1)           # units, per type
+
+    TABLES = ("u_x2", "u_pitch", "v_x2", "v_pitch", "kind")
+
+    def tables(self, device):
+        """The five int32 tables on ``device`` (dict by name); the upload happens once per device."""
+        device = torch.device(device)
+        if device not in self._device:
+            self._device[device] = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device) for k in self.TABLES}
+        return self._device[device]
+
+    @classmethod
+    def uniform(cls, shape, u_pitch, v_pitch, n_sensors=40, unit_mm=5e-4):
+        """One type, every cell ``u_pitch`` x ``v_pitch`` units, ``n_sensors`` sensors of ``shape = (H, W)`` cells."""
+        Hh, Ww = shape
+        return cls(np.full((1, Hh), int(u_pitch)), np.full((1, Ww), int(v_pitch)), np.zeros(int(n_sensors), np.int64), unit_mm)
+
+    @classmethod
+    def belle2(cls, shape=(250, 768), n_sensors=40):
+        """The nominal Belle II PXD in units of 0.5 um: u pitch 50 um everywhere; v pitch fine on the cells 0 .. 255 and coarse on 256 .. 767
+        -- 55 / 60 um on the sensors 0 .. 15 (layer 1, 12.5 x 44.8 mm sensitive), 70 / 85 um on the sensors 16 .. 39 (layer 2, 12.5 x 61.44 mm),
+        the sensor order of the reference's ``create_g1.py:95``.  These are design values written down from memory: the reference holds no
+        geometry, and neither they nor the end that carries the fine pitch have been checked against basf2.  Pass the true tables of the
+        conditions database to ``PXDGeometry`` where it matters.  Only 250 x 768 cells and 40 sensors have this geometry."""
+        if tuple(shape) != (250, 768) or int(n_sensors) != 40:
+            raise ValueError(f"PXDGeometry.belle2: the PXD has 40 sensors of 250 x 768 cells, not {n_sensors} of {tuple(shape)}")
+        v = np.array([[110] * 256 + [120] * 512, [140] * 256 + [170] * 512])
+        return cls(np.full((2, 250), 100), v, np.array([0] * 16 + [1] * 24))
+
+
+class PXDHits(_PXDProduct):
+    """Device-side result of ``pxd_hits``: the ``PXDClusterPositions`` it came from (``positions``), the ``geometry`` and ``head_tail``; per
+    cluster (row j of the table, the first ``clusters.total`` rows written) the physical moments ``pu`` / ``pv`` int64, the first column
+    ``v_start`` int32 and the edge charges ``qh_u`` / ``qt_u`` / ``qh_v`` / ``qt_v`` int32; per accepted cluster, in the order of
+    ``positions.cluster`` (the first ``total`` rows written), ``u`` / ``v`` fp32 in geometry units from the sensor centre and ``flags`` uint8
+    (bit 0 / 1: u / v used head-tail, bit 2 / 3: u / v was clamped to the cluster's extent).  All ``[capacity]``; ``counts`` / ``total`` are
+    those of the positions: the accepted clusters are the hits."""
+    _again = lambda self, capacity: pxd_hits(self.images, self.geometry, self.head_tail, self.threshold, self.seed_cut, self.charge_cut, capacity,
+                                             self.n_sensors)
+    PER_CLUSTER, PER_HIT = ("pu", "pv", "v_start", "qh_u", "qt_u", "qh_v", "qt_v"), ("u", "v", "flags")
+
+    def __init__(self, positions, geometry, head_tail, **arrays):
+        self.positions, self.geometry, self.head_tail = positions, geometry, head_tail
+        self.seed_cut, self.charge_cut = positions.seed_cut, positions.charge_cut
+        vars(self).update(arrays)
+        self._set_header(positions.header, positions)
+
+    def cpu(self):
+        """One read-back (``pxd_read_back``: one copy, one wait) -> dict of NumPy arrays trimmed to the true total, one entry per hit:
+        ``cluster``, ``sensor``, ``event``, ``u``, ``v`` (fp32, geometry units), ``u_mm``, ``v_mm`` (float64: ``u.astype(float64) *
+        unit_mm``), ``charge``, ``seed``, ``size``, ``size_u``, ``size_v``, ``u_start``, ``v_start`` (first row / column of the cluster),
+        ``flags``; plus ``counts [N]``.  Never truncated (``_host_columns``)."""
+        N, Hh, Ww = self.shape
+        host = self._host_columns(lambda: dict(digit_header=self.positions.clusters.digits.header, header=self.header,
+                                               cluster=self.positions.cluster, u=self.u, v=self.v, flags=self.flags, v_start=self.v_start,
+                                               **{k: getattr(self.positions.clusters, k) for k in PXDClusters.TABLE}))
+        total = int(host["header"][N])
+        cluster = host["cluster"][:total].copy()
+        image, rest = np.divmod(host["first"][cluster], np.int32(Hh * Ww))
+        out = {k: host[k][:total].copy() for k in ("u", "v", "flags")}
+        return dict(out, cluster=cluster, sensor=(image % self.n_sensors).astype(np.int32), event=(image // self.n_sensors).astype(np.int32),
+                    u_mm=out["u"].astype(np.float64) * self.geometry.unit_mm, v_mm=out["v"].astype(np.float64) * self.geometry.unit_mm,
+                    u_start=(rest // np.int32(Ww)).astype(np.int32), counts=host["header"][:N].copy(),
+                    **{k: host[k][cluster] for k in ("charge", "seed", "size", "size_u", "size_v", "v_start")})
+
+
+def pxd_hits(images_or_product, geometry, head_tail=3, threshold=0.0, seed_cut=0, charge_cut=0, capacity=None, n_sensors=40):
+    """Hits of a batch of sensor images ``[N, H, W]`` (fp32 or uint8 device tensor: ``pxd_cluster_positions(images, threshold, seed_cut,
+    charge_cut, capacity, n_sensors)`` runs first), of an existing ``PXDClusters`` (positions with the cuts run first) or of an existing
+    ``PXDClusterPositions`` (its cuts, threshold, capacity and sensors hold): the position of every accepted cluster in the local frame of
+    its sensor, origin at the sensor centre, in the integer units of ``geometry`` (a ``PXDGeometry``; ``PXDHits.cpu()`` scales to mm in
+    float64).  This is the project's own statement of the head-tail form; agreement with basf2 is not claimed.  Along one axis a cluster of
+    charge ``Q`` covers the cells ``lo .. hi`` (``s`` of them); ``x2`` / ``p`` are the doubled centres and pitches of its sensor's type:
+
+    * ``s < head_tail`` (or ``head_tail == 0``: never head-tail; otherwise ``head_tail >= 3``): centre of gravity, ``num = sum q * x2[cell]``,
+      ``den = 2 * Q``;
+    * else head-tail with the charges ``q_head`` / ``q_tail`` in the cells ``lo`` / ``hi`` and ``D = Q - q_head - q_tail``:
+      ``num = (x2[lo] + x2[hi]) * D + 2 * (q_tail * p[hi] - q_head * p[lo]) * (s - 2)``, ``den = 4 * D`` -- that is ``(x_lo + x_hi) / 2 +
+      (q_tail * p_hi - q_head * p_lo) / (2 * q_centre)`` with ``q_centre = D / (s - 2)``;
+    * the result is clamped, in integers, to ``[x2[lo] - p[lo], x2[hi] + p[hi]] / 2``: a hit lies inside its cluster's bounding box;
+    * ``position = float32(float64(num) / float64(den))``: ``num`` and ``den`` are exact integers below 2^53 (``PXDGeometry``), so the same
+      recipe on the host gives the same bits; bit-identical run to run.
+
+    Position errors and signal-to-noise cuts (both need a per-pixel noise map), global coordinates and a basf2 writer are out of scope.
+    Launches on the current stream, neither synchronises nor copies; with ``capacity`` given it can be captured into a HIP graph.  When the
+    digit total exceeds the capacity the device result covers the first ``capacity`` digits; ``PXDHits.cpu()`` reruns instead of handing
+    back a truncated event.  ``ValueError`` when the geometry's ``H``, ``W`` or ``S`` are not the batch's."""
+    H.require_gpu()
+    head_tail = int(head_tail)
+    if head_tail != 0 and head_tail < 3:
+        raise ValueError(f"pxd_hits: head_tail = {head_tail} is neither 0 (never) nor >= 3")
+    if not isinstance(geometry, PXDGeometry):
+        raise TypeError("pxd_hits: geometry must be a PXDGeometry")
+    p = images_or_product
+    if not isinstance(p, PXDClusterPositions):
+        p = pxd_cluster_positions(p, threshold, seed_cut, charge_cut, capacity, n_sensors)
+    c, d = p.clusters, p.clusters.digits
+    N, Hh, Ww = p.shape
+    if (geometry.H, geometry.W, geometry.S) != (Hh, Ww, p.n_sensors):
+        raise ValueError(f"pxd_hits: the geometry has {geometry.S} sensors of {geometry.H} x {geometry.W} cells, the batch {p.n_sensors} of {Hh} x {Ww}")
+    dev, C = p.cluster.device, p.capacity
+    new = lambda dtype: torch.empty(C, dtype=dtype, device=dev)
+    out = dict(pu=new(torch.int64), pv=new(torch.int64), **{k: new(torch.int32) for k in PXDHits.PER_CLUSTER[2:]}, u=new(torch.float32),
+               v=new(torch.float32), flags=new(torch.uint8))
+    t = geometry.tables(dev)
+    with torch.cuda.device(dev):
+        H.call("ieagan_pxd_hits", *_ptrs(C, d.index, d.charge, c.label), d.total.data_ptr(), *_ptrs(C, c.first, c.charge, c.size_u, c.size_v),
+               c.total.data_ptr(), *_ptrs(C, p.cluster), p.total.data_ptr(), *(t[k].data_ptr() for k in PXDGeometry.TABLES), N, Hh, Ww, p.n_sensors,
+               geometry.K, C, head_tail, *_ptrs(C, *(out[k] for k in PXDHits.PER_CLUSTER + PXDHits.PER_HIT)), None, H.stream())
+    return PXDHits(p, geometry, head_tail, **out)
+
+
+# the columns of the hit file of ``produce.py --hits`` and their types: the events, then nine columns of the hits
+HIT_COLUMNS = dict(event_offsets=np.int64, sensor=np.uint8, u_mm=np.float32, v_mm=np.float32, charge=np.int32, seed=np.uint8, size=np.uint16,
+                   size_u=np.uint16, size_v=np.uint16, flags=np.uint8)
+
+
+def write_hits(path, event_offsets, sensor, u_mm, v_mm, charge, seed, size, size_u, size_v, flags, unit_mm=5e-4):
+    """The hit file of ``produce.py --hits`` (``.npz``): ``event_offsets`` int64 ``[events + 1]`` (the hits of event ``e`` are
+    ``[event_offsets[e], event_offsets[e + 1])``), per hit ``sensor`` uint8, ``u_mm`` / ``v_mm`` float32 (local position from the sensor
+    centre), ``charge`` int32, ``seed`` uint8, ``size`` / ``size_u`` / ``size_v`` uint16, ``flags`` uint8 (``PXDHits``), and the scalar
+    ``unit_mm`` of the geometry the positions were computed in."""
+    event_offsets = np.asarray(event_offsets, np.int64)
+    cols = dict(zip(list(HIT_COLUMNS)[1:], map(np.asarray, (sensor, u_mm, v_mm, charge, seed, size, size_u, size_v, flags))))
+    if event_offsets.ndim != 1 or event_offsets.size < 1 or event_offsets[0] != 0 or (np.diff(event_offsets) < 0).any():
+        raise ValueError("write_hits: event_offsets must start at 0 and not decrease")
+    for k, v in cols.items():
+        if v.ndim != 1 or v.size != event_offsets[-1]:
+            raise ValueError(f"write_hits: {k} has {v.size} entries, event_offsets ends at {event_offsets[-1]}")
+    for k in ("sensor", "seed", "size", "size_u", "size_v", "flags") if event_offsets[-1] else ():
+        if cols[k].min() < 0 or cols[k].max() > np.iinfo(HIT_COLUMNS[k]).max:
+            raise ValueError(f"write_hits: a {k} value does not fit the file's {np.dtype(HIT_COLUMNS[k]).name} column")
+    with open(path, "wb") as fh:
+        np.savez(fh, event_offsets=event_offsets, unit_mm=np.float64(unit_mm), **{k: v.astype(HIT_COLUMNS[k]) for k, v in cols.items()})
+
+
+def read_hits(path):
+    """The arrays of a ``write_hits`` file as a dict: the ``HIT_COLUMNS`` and ``unit_mm`` (float)."""
+    with np.load(path) as t:
+        missing = [k for k in list(HIT_COLUMNS) + ["unit_mm"] if k not in t.files]
+        if missing:
+            raise ValueError(f"read_hits: {path} is no hit file of write_hits, it lacks {missing}")
+        return dict({k: t[k] for k in HIT_COLUMNS}, unit_mm=float(t["unit_mm"]))
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -494,6 +494,36 @@ int ieagan_pxd_cluster_maps(const int* cluster, const int* accepted_total, const
                             const int* digit_total, int N, int H, int W, int n_sensors, long capacity, unsigned long long* count,
                             unsigned long long* charge, unsigned long long* overflow, void* stream);
 
+/* ---- PXD hits: head-tail cluster positions in local sensor coordinates (pxd_hits.hip) ------------------
+ * Input: one ieagan_pxd_digits + ieagan_pxd_clusters + ieagan_pxd_cluster_positions result of a batch [N, H, W] (index / charge / label per
+ * digit, first / ccharge / size_u / size_v per cluster, the accepted list `cluster` with accepted_total = the positions' `total`; every
+ * array [capacity], every total read on the device) and the geometry tables of K sensor types, int32 on the device:
+ *   u_pitch [K][H], v_pitch [K][W]   pitch of every cell in integer geometry units, 1 .. 4095, each row summing to less than 2^20
+ *   u_x2 [K][H], v_x2 [K][W]         doubled, centred cell centres: x2[k] = 2 * sum(pitch[:k]) + pitch[k] - sum(pitch)
+ *   kind [n_sensors]                 type of a sensor, 0 .. K-1; the type of cluster j is kind[(first[j] / (H*W)) % n_sensors]
+ * The launcher cannot see device memory: the content of the tables is checked by the host (pxd.PXDGeometry).  A type outside 0 .. K-1 never
+ * indexes a table (such a cluster gets position 0).  Per cluster j < T = *cluster_total, over its digits (charge q, row r, column c):
+ *   pu [T], pv [T] int64      sum q * u_x2[r], sum q * v_x2[c]                      v_start [T] int32   smallest column
+ *   qh_u, qt_u, qh_v, qt_v [T] int32   summed charge in the first / last row and in the first / last column of the cluster's extent
+ * Per accepted cluster a < A = *accepted_total, j = cluster[a], along each axis (u: rows, cells lo = row of first[j] .. hi = lo + size_u - 1,
+ * the u tables; v: columns from v_start[j], the v tables) with Q = ccharge[j], m the moment, s the extent, x2 / p the type's tables:
+ *   s < head_tail or head_tail == 0:   num = m, den = 2 Q                                                        (centre of gravity)
+ *   else, D = Q - qh - qt:             num = (x2[lo] + x2[hi]) D + 2 (qt p[hi] - qh p[lo]) (s - 2), den = 4 D     (head-tail)
+ *   2 num < den (x2[lo] - p[lo]):  num = x2[lo] - p[lo], den = 2;   2 num > den (x2[hi] + p[hi]):  num = x2[hi] + p[hi], den = 2   (clamp)
+ *   u [A], v [A] fp32   (float)((double)num / (double)den) in geometry units, origin at the sensor centre; |num| < 2^53, so this is the
+ *                       correctly rounded quotient.  head_tail is 0 (never) or >= 3.
+ *   flags [A] uint8     bit 0 / 1: u / v used head-tail; bit 2 / 3: u / v was clamped
+ * Nothing is written outside [0, T) of the per-cluster and [0, A) of the per-hit arrays (capacity 0: every [capacity] array may be NULL).
+ * Integer atomics and shuffles only, no float is summed: two calls on the same input write the same bytes.  The launch shapes depend on the
+ * capacity alone, no synchronise, no copy (graph-capturable).
+ * scratch: ieagan_pxd_hits_scratch(N, H, W, capacity) int32 words -- 0 today (every intermediate is an output), scratch may then be NULL. */
+long ieagan_pxd_hits_scratch(int N, int H, int W, long capacity);
+int ieagan_pxd_hits(const int* index, const unsigned char* charge, const int* label, const int* digit_total, const int* first,
+                    const int* ccharge, const int* size_u, const int* size_v, const int* cluster_total, const int* cluster,
+                    const int* accepted_total, const int* u_x2, const int* u_pitch, const int* v_x2, const int* v_pitch, const int* kind, int N,
+                    int H, int W, int n_sensors, int K, long capacity, int head_tail, long long* pu, long long* pv, int* v_start, int* qh_u,
+                    int* qt_u, int* qh_v, int* qt_v, float* u, float* v, unsigned char* flags, int* scratch, void* stream);
+
 /* ---- sparse event store -> network input (pxd_events.hip) --------------------------------------------
  * A store holds n_events events of PXD digits on the device (the columns of the produce.py file, flattened):
  *   pos [n_digits] int32       (sensor * H + ucell) * W + vcell of a digit inside its event, STRICTLY ascending inside an event;
