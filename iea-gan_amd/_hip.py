@@ -164,6 +164,8 @@ _SIGS = {
     "ieagan_pxd_hits_scratch": [i, i, i, l],
     "ieagan_pxd_event_ingest": [vp, vp, vp, l, i, vp, i, i, i, i, i, vp, f, vp, vp],
     "ieagan_pxd_event_dense": [vp, vp, vp, l, i, vp, i, i, i, i, vp, vp],
+    "ieagan_pxd_event_overlay": [vp, vp, vp, l, i, vp] * 2 + [i, i, i, i, l, vp, vp, vp, vp, vp],
+    "ieagan_pxd_event_overlay_scratch": [i, l],
     "ieagan_ortho_ksplit": [],
     "ieagan_ortho_grad": [vp, vp, vp, vp, i, vp, i, vp, l, f, vp],
     "ieagan_selftest_tr_read": [vp, vp, vp],

@@ -2,7 +2,8 @@
 (csrc/pxd_stats.hip), event production as sparse digits (csrc/pxd_digits.hip), clusters of the digits and their spectra
 (csrc/pxd_clusters.hip), cluster reconstruction -- cuts, charge-weighted positions, per-sensor position maps (csrc/pxd_reco.hip) --, hits in the local
 frame of a sensor with a geometry given as data (csrc/pxd_hits.hip), the event and hit files of ``produce.py`` and the store that keeps such a file's events on the device and expands them into the network input
-(csrc/pxd_events.hip).  ``utils`` re-exports every name defined here."""
+(csrc/pxd_events.hip), and the overlay of the events of two stores, pixel by pixel in the sparse format (csrc/pxd_overlay.hip).  ``utils``
+re-exports every name defined here."""
 from __future__ import annotations
 
 import numpy as np
@@ -946,6 +947,43 @@ class PXDEventStore:
         offsets = np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.int64)
         return cls(offsets, np.concatenate(pos), np.concatenate(charge), shape, n_sensors, device)
 
+    @classmethod
+    def _from_device(cls, counts, offsets, pos, charge, shape, n_sensors):
+        """A store over tensors that are on the device already (``offsets`` int64 ``[events + 1]``, ``pos`` int32, ``charge`` uint8) and the
+        host copy of the digits per event, ``counts``; the caller vouches for the store's contract.  Nothing is copied."""
+        self = cls.__new__(cls)
+        self.shape, self.n_sensors, self.device = (int(shape[0]), int(shape[1])), int(n_sensors), offsets.device
+        self.counts, self.offsets, self.pos, self.charge = np.asarray(counts, np.int64), offsets, pos, charge
+        return self
+
+    @classmethod
+    def from_digits(cls, digits):
+        """The ``PXDDigits`` of a batch of whole events (``pxd_digits`` of generated or recorded images) -> a store of those events, made on
+        the device: ``pos = index % (S * H * W)``, the charges as they stand (a view of the digits' tensor), the offsets from the counts
+        summed per event.  The one read-back is the digit header (``counts``, ``total``: 4 bytes an image), which also triggers the usual
+        rerun with ``capacity = total`` when the digits did not fit; no digit crosses PCIe.  ``ValueError`` for digits made with a negative
+        threshold (with ``threshold >= 0`` every charge of ``pxd_digits`` is in 1 .. 255 and the positions ascend strictly: the store's
+        contract holds by construction)."""
+        if not isinstance(digits, PXDDigits):
+            raise TypeError("PXDEventStore.from_digits takes the PXDDigits of pxd_digits")
+        if not digits.threshold >= 0:
+            raise ValueError(f"PXDEventStore.from_digits: the digits were made with threshold = {digits.threshold}, not >= 0")
+        (N, Hh, Ww), S = digits.shape, digits.n_sensors
+        header = pxd_read_back(header=digits.header)["header"]
+        total = int(header[N])
+        if total > digits.capacity:
+            digits._grow(total)
+        with torch.cuda.device(digits.header.device):
+            pos = torch.remainder(digits.index[:total], S * Hh * Ww)
+            per_event = digits.counts.view(-1, S).sum(1, dtype=torch.int64)
+            offsets = torch.cat([per_event.new_zeros(1), torch.cumsum(per_event, 0)])
+        return cls._from_device(header[:N].reshape(-1, S).sum(1), offsets, pos, digits.charge[:total], (Hh, Ww), S)
+
+    def overlay(self, event_ids, other, other_ids=None, capacity=None):
+        """The events ``event_ids`` of this store with the events ``other_ids`` (default: the same numbers) of ``other`` laid over them, as a
+        new store: ``pxd_overlay(self, event_ids, other, other_ids, capacity).store()``."""
+        return pxd_overlay(self, event_ids, other, other_ids, capacity).store()
+
     def __len__(self):
         return int(self.counts.size)
 
@@ -1017,3 +1055,97 @@ class PXDEventStore:
             out = torch.empty(E * self.n_sensors, *self.shape, dtype=torch.uint8, device=self.device)
             H.call("ieagan_pxd_event_dense", *self._store_args(ids, E), out.data_ptr(), H.stream())
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# background overlay: the events of two stores added pixel by pixel, in the sparse format (csrc/pxd_overlay.hip)
+# ---------------------------------------------------------------------------------------------------------
+def _n_ids(ids):
+    """The number of event ids in what ``PXDEventStore._ids`` takes, found on the host."""
+    return int(ids.numel()) if isinstance(ids, torch.Tensor) else int(np.asarray(ids).size)
+
+
+class PXDOverlay:
+    """Device-side result of ``pxd_overlay``: ``pos`` int32 ``[capacity]``, ``charge`` uint8 ``[capacity]`` -- the merged events back to back,
+    only the first ``min(total, capacity)`` digits written -- and ``offsets`` int64 ``[E + 1]``, the start of every merged event and the
+    total, the true numbers whatever the capacity; plus ``capacity``, ``shape`` and ``n_sensors``."""
+
+    def __init__(self, a, a_ids, b, b_ids, capacity, pos, charge, offsets):
+        self._pairs = (a, a_ids, b, b_ids)          # the stores and the ids as the caller gave them
+        self.capacity, self.shape, self.n_sensors = capacity, a.shape, a.n_sensors
+        self.pos, self.charge, self.offsets, self._host = pos, charge, offsets, None
+
+    def _host_offsets(self):
+        """``offsets`` on the host: one ``pxd_read_back`` (8 * (E + 1) bytes, one wait), kept.  When the total exceeds the capacity the overlay
+        is run again with ``capacity = total`` and adopted (a second read-back, on that path only): the host never sees a truncated event."""
+        if self._host is None:
+            host = pxd_read_back(offsets=self.offsets)["offsets"]
+            if host[-1] > self.capacity:
+                a, a_ids, b, b_ids = self._pairs
+                again = pxd_overlay(a, a_ids, b, b_ids, int(host[-1]))
+                self.capacity, self.pos, self.charge, self.offsets = again.capacity, again.pos, again.charge, again.offsets
+                host = pxd_read_back(offsets=self.offsets)["offsets"]
+            self._host = host
+        return self._host
+
+    def store(self):
+        """The merged events as a ``PXDEventStore`` over the first ``total`` digits: the offsets are read back (``_host_offsets``) and give
+        the new store's ``counts``; the digits stay where they are, none goes through the host."""
+        host = self._host_offsets()
+        total = int(host[-1])
+        return PXDEventStore._from_device(np.diff(host), self.offsets, self.pos[:total], self.charge[:total], self.shape, self.n_sensors)
+
+    def shared(self):
+        """int64 ``[E]``: the pixels of every pair that held a digit in both events, ``na + nb - n_out``, on the host from the three count
+        arrays (device ids are read back for it; an id outside its store counts no digit)."""
+        out = np.diff(self._host_offsets())
+        a, a_ids, b, b_ids = self._pairs
+        n = 0
+        for store, ids in ((a, a_ids), (b, b_ids)):
+            ids = (ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)).reshape(-1).astype(np.int64)
+            inside = (ids >= 0) & (ids < len(store))
+            n = n + np.where(inside, store.counts[np.where(inside, ids, 0)] if len(store) else 0, 0)
+        return (n - out).astype(np.int64)
+
+
+def pxd_overlay(a, a_ids, b, b_ids=None, capacity=None):
+    """Overlay of sparse events on the device (csrc/pxd_overlay.hip): merged event ``e`` holds every pixel that is a digit in event
+    ``a_ids[e]`` of the store ``a`` or in event ``b_ids[e]`` (default: ``a_ids[e]``) of the store ``b``, in ascending position; a pixel of
+    one event keeps its charge, a pixel of both gets ``min(qa + qb, 255)``, the ADC's saturation -- what the clamped sum of the dense images
+    gives, without a dense image.  Ids as everywhere in ``PXDEventStore``: host ids are range-checked, an int32 device tensor is taken as it
+    is and an id outside its store is an empty event.
+
+    ``capacity`` (digits of the result) defaults, with host ids, to the digits of all the events named, a bound the host knows; with a
+    device id tensor on either side it must be given.  Launches on the current stream, neither synchronises nor copies; with device ids it
+    can be captured into a HIP graph.  ``offsets`` of the returned ``PXDOverlay`` always holds the true numbers; its ``store()`` reruns with a
+    larger capacity instead of truncating.  ``ValueError`` when the stores differ in ``shape``, ``n_sensors`` or ``device``, when the id lists
+    differ in length and for a missing or negative capacity."""
+    if not isinstance(a, PXDEventStore) or not isinstance(b, PXDEventStore):
+        raise TypeError("pxd_overlay: a and b must be PXDEventStores")
+    for k in ("shape", "n_sensors", "device"):
+        if getattr(a, k) != getattr(b, k):
+            raise ValueError(f"pxd_overlay: the stores differ in {k}: {getattr(a, k)} and {getattr(b, k)}")
+    if b_ids is None:
+        b_ids = a_ids
+    if _n_ids(a_ids) != _n_ids(b_ids):
+        raise ValueError(f"pxd_overlay: {_n_ids(a_ids)} ids into a, {_n_ids(b_ids)} into b")
+    on_device = any(isinstance(i, torch.Tensor) and i.is_cuda for i in (a_ids, b_ids))
+    if capacity is None and on_device:
+        raise ValueError("pxd_overlay: with a device id tensor the host does not know the events, capacity= is required")
+    if capacity is not None and int(capacity) < 0:
+        raise ValueError("pxd_overlay: capacity is negative")
+    H.require_gpu()
+    ia, E = a._ids(a_ids, "pxd_overlay (a_ids)")
+    ib, _ = b._ids(b_ids, "pxd_overlay (b_ids)")
+    if capacity is None:
+        capacity = sum(int(s.counts[np.asarray(i, np.int64).reshape(-1)].sum()) for s, i in ((a, a_ids), (b, b_ids)) if len(s))
+    capacity = int(capacity)
+    dev = a.device
+    with torch.cuda.device(dev):
+        pos = torch.empty(capacity, dtype=torch.int32, device=dev)
+        charge = torch.empty(capacity, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(E + 1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(H.lib().ieagan_pxd_event_overlay_scratch(E, capacity), dtype=torch.int32, device=dev)
+        H.call("ieagan_pxd_event_overlay", *a._store_args(ia, E)[:6], *b._store_args(ib, E)[:6], E, a.n_sensors, a.shape[0], a.shape[1], capacity,
+               *_ptrs(capacity, pos, charge), offsets.data_ptr(), scratch.data_ptr(), H.stream())
+    return PXDOverlay(a, a_ids, b, b_ids, capacity, pos, charge, offsets)

@@ -546,6 +546,25 @@ int ieagan_pxd_event_ingest(const int* pos, const unsigned char* charge, const l
 int ieagan_pxd_event_dense(const int* pos, const unsigned char* charge, const long* offsets, long n_digits, int n_events,
                            const int* event_ids, int E, int S, int H, int W, unsigned char* out, void* stream);
 
+/* ---- background overlay: two sparse events added pixel by pixel (pxd_overlay.hip) ------------------------
+ * Two stores of the contract above (a_*, b_*; they may be the same store), E pairs of events given by a_ids / b_ids [E] int32, read ON THE
+ * DEVICE (an id outside its store is an empty event).  Output event e is the union of the positions of A[a_ids[e]] and B[b_ids[e]],
+ * ascending; a position in one list keeps its charge, a position in both gets min(qa + qb, 255).  A store again:
+ *   out_pos [capacity] int32, out_charge [capacity] uint8   the events back to back in the order of e; only digits with output index
+ *                                                           < capacity are written (capacity 0: both may be NULL)
+ *   out_offsets [E + 1] int64                               start of every output event and the total: the TRUE numbers whatever the capacity
+ * 1 <= E <= 65535, S * H * W < 2^31; a call merges fewer than 2^31 input digits.  A merge of sorted lists, work proportional to the digits:
+ * no dense image, no atomics, no floats, one writer per output element -- two calls write the same bytes.  Memory safety does not depend
+ * on the content of the stores (ranges clipped to [0, n_digits], every probe of a search inside the range it was given, nothing written
+ * at or beyond capacity): a store that breaks its contract gives wrong digits, never a wrong address.  Four launches on `stream` whose
+ * shapes depend on (E, capacity) alone, every count read on the device, no synchronise, no copy (graph-capturable; a replay reads the
+ * current ids).  scratch: ieagan_pxd_event_overlay_scratch(E, capacity) int32 words. */
+long ieagan_pxd_event_overlay_scratch(int E, long capacity);
+int ieagan_pxd_event_overlay(const int* a_pos, const unsigned char* a_charge, const long* a_offsets, long a_digits, int a_events,
+                             const int* a_ids, const int* b_pos, const unsigned char* b_charge, const long* b_offsets, long b_digits,
+                             int b_events, const int* b_ids, int E, int S, int H, int W, long capacity, int* out_pos,
+                             unsigned char* out_charge, long* out_offsets, int* scratch, void* stream);
+
 /* ---- orthogonal regularisation (ortho.hip) -------------------------------------------------------
  * Replaces utils.ortho (reference utils/__init__.py:843-859) for ALL weight matrices of a network in one call:
  * grad[l] += 2*strength * ((W_l W_l^T) (.) (1 - I)) W_l, fp32, on the flat parameter / gradient arenas.
