@@ -27,6 +27,10 @@ PXD_CLUSTER_COLUMNS = {"size_spectrum": (0, 64), "charge_spectrum": (64, 256), "
                        "size_v_spectrum": (608, 32)}
 PXD_CLUSTER_BINS = 640
 PXD_MAP_U, PXD_MAP_V = 25, 48       # bins of the ieagan_pxd_cluster_maps grid over the rows / columns of a sensor (csrc/pxd_reco.hip)
+# columns of one sensor's row of the ieagan_pxd_match_stats table (csrc/pxd_match.hip): name -> (first column, bins)
+PXD_MATCH_COUNTERS = ("hits", "matched", "changed", "shared", "lost")
+PXD_MATCH_COLUMNS = {"residual_u": (5, 64), "residual_v": (69, 64), "purity": (133, 32)}
+PXD_MATCH_BINS = 165
 PROLOGUE_BWD_SLOTS = 64  # include/ieagan_hip.h: IEAGAN_PROLOGUE_BWD_SLOTS
 AUG_SLOTS = 128         # include/ieagan_hip.h: IEAGAN_AUG_SLOTS (per-image partial-sum slots of the DiffAugment entry points)
 BNB_REPL = 8            # replicas of the per-image accumulators of a BatchNorm-backward dgrad launch (common.h)
@@ -166,6 +170,9 @@ _SIGS = {
     "ieagan_pxd_event_dense": [vp, vp, vp, l, i, vp, i, i, i, i, vp, vp],
     "ieagan_pxd_event_overlay": [vp, vp, vp, l, i, vp] * 2 + [i, i, i, i, l, vp, vp, vp, vp, vp],
     "ieagan_pxd_event_overlay_scratch": [i, l],
+    "ieagan_pxd_match": [vp] * 21 + [i, i, i, l, l] + [vp] * 12,
+    "ieagan_pxd_match_scratch": [i, i, i, l],
+    "ieagan_pxd_match_stats": [vp] * 17 + [i, i, i, i, l, l, i] + [vp] * 3,
     "ieagan_ortho_ksplit": [],
     "ieagan_ortho_grad": [vp, vp, vp, vp, i, vp, i, vp, l, f, vp],
     "ieagan_selftest_tr_read": [vp, vp, vp],

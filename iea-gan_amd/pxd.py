@@ -2,8 +2,8 @@
 (csrc/pxd_stats.hip), event production as sparse digits (csrc/pxd_digits.hip), clusters of the digits and their spectra
 (csrc/pxd_clusters.hip), cluster reconstruction -- cuts, charge-weighted positions, per-sensor position maps (csrc/pxd_reco.hip) --, hits in the local
 frame of a sensor with a geometry given as data (csrc/pxd_hits.hip), the event and hit files of ``produce.py`` and the store that keeps such a file's events on the device and expands them into the network input
-(csrc/pxd_events.hip), and the overlay of the events of two stores, pixel by pixel in the sparse format (csrc/pxd_overlay.hip).  ``utils``
-re-exports every name defined here."""
+(csrc/pxd_events.hip), the overlay of the events of two stores, pixel by pixel in the sparse format (csrc/pxd_overlay.hip), and the match of
+the signal hits to the hits of the mixed events, hit by hit (csrc/pxd_match.hip).  ``utils`` re-exports every name defined here."""
 from __future__ import annotations
 
 import numpy as np
@@ -1149,3 +1149,207 @@ def pxd_overlay(a, a_ids, b, b_ids=None, capacity=None):
         H.call("ieagan_pxd_event_overlay", *a._store_args(ia, E)[:6], *b._store_args(ib, E)[:6], E, a.n_sensors, a.shape[0], a.shape[1], capacity,
                *_ptrs(capacity, pos, charge), offsets.data_ptr(), scratch.data_ptr(), H.stream())
     return PXDOverlay(a, a_ids, b, b_ids, capacity, pos, charge, offsets)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# signal-hit matching under background: what became of every signal hit once background lay over it (csrc/pxd_match.hip)
+# ---------------------------------------------------------------------------------------------------------
+PXD_MATCHED, PXD_CHANGED, PXD_SHARED = 1, 2, 4          # the bits of ``PXDMatch.flags``
+PXD_RESIDUAL_BINS, PXD_PURITY_BINS = 64, 32
+
+
+def _same_geometry(a, b):
+    return a is b or (isinstance(a, PXDGeometry) and isinstance(b, PXDGeometry) and a.unit_mm == b.unit_mm and
+                      all(np.array_equal(getattr(a, k), getattr(b, k)) for k in PXDGeometry.TABLES))
+
+
+def _check_match_sides(signal, mixed, who="pxd_match"):
+    """Both sides are ``PXDHits`` made the same way over batches of the same shape on one device, or ``TypeError`` / ``ValueError``."""
+    if not isinstance(signal, PXDHits) or not isinstance(mixed, PXDHits):
+        raise TypeError(f"{who}: signal and mixed must be the PXDHits of pxd_hits")
+    for k in ("shape", "n_sensors", "threshold", "seed_cut", "charge_cut", "head_tail"):
+        if getattr(signal, k) != getattr(mixed, k):
+            raise ValueError(f"{who}: the two PXDHits differ in {k}: {getattr(signal, k)} and {getattr(mixed, k)}")
+    if not _same_geometry(signal.geometry, mixed.geometry):
+        raise ValueError(f"{who}: the two PXDHits differ in geometry")
+    if signal.header.device != mixed.header.device:
+        raise ValueError(f"{who}: the two PXDHits differ in device: {signal.header.device} and {mixed.header.device}")
+
+
+class PXDMatch:
+    """Device-side result of ``pxd_match``: the two ``PXDHits`` (``signal``, ``mixed``); per signal cluster (row j of the signal table, the
+    first ``signal.positions.clusters.total`` rows written) ``found`` / ``lo`` / ``hi`` int32 ``[signal.capacity]``; per mixed cluster
+    ``signal_size`` / ``signal_charge`` / ``n_signal`` int32 ``[mixed.capacity]``; per signal hit, in the order of
+    ``signal.positions.cluster`` (the first ``signal.total`` rows written), ``mixed_hit`` int32, ``flags`` uint8 (``PXD_MATCHED``,
+    ``PXD_CHANGED``, ``PXD_SHARED``), ``du`` / ``dv`` fp32 in geometry units.  ``header`` / ``counts`` / ``total`` are those of the signal
+    hits: the product has one row per signal hit."""
+    PER_SIGNAL_CLUSTER, PER_MIXED_CLUSTER, PER_HIT = ("found", "lo", "hi"), ("signal_size", "signal_charge", "n_signal"), ("mixed_hit", "flags", "du", "dv")
+
+    def __init__(self, signal, mixed, **arrays):
+        self.signal, self.mixed = signal, mixed
+        self.shape, self.n_sensors, self.geometry = signal.shape, signal.n_sensors, signal.geometry
+        self.header, self.counts, self.total = signal.header, signal.counts, signal.total
+        vars(self).update(arrays)
+
+    def _columns(self):
+        s, m = self.signal, self.mixed
+        sc, mc = s.positions.clusters, m.positions.clusters
+        return dict(digit_header=sc.digits.header, mixed_digit_header=mc.digits.header, header=s.header, cluster_header=sc.header,
+                    mixed_cluster_header=mc.header, cluster=s.positions.cluster, first=sc.first, size=sc.size, charge=sc.charge,
+                    mixed_charge=mc.charge, **{k: getattr(self, k) for k in self.PER_SIGNAL_CLUSTER + self.PER_MIXED_CLUSTER + self.PER_HIT})
+
+    def cpu(self):
+        """One read-back (``pxd_read_back``: one copy, one wait) -> dict of NumPy arrays trimmed to the true totals, one entry per signal
+        hit: ``cluster`` (row of the signal table), ``sensor``, ``event``, ``mixed_hit``, ``flags``, ``du``, ``dv`` (fp32, geometry units),
+        ``du_mm``, ``dv_mm`` (float64: ``du.astype(float64) * unit_mm``), ``found``, ``size``, ``charge`` (of the signal cluster),
+        ``match`` and ``hi`` (its smallest and largest mixed cluster, -1: none) and, of the mixed cluster ``match`` (0 where there is
+        none), ``mixed_charge``, ``signal_charge``, ``signal_size``, ``n_signal``; plus ``counts [N]``.  Never truncated: when a side's
+        digit total exceeds its capacity that side is grown and the match run again (a second read-back, on that path only)."""
+        N, Hh, Ww = self.shape
+        host = pxd_read_back(**self._columns())
+        grown = False
+        for side, key in ((self.signal, "digit_header"), (self.mixed, "mixed_digit_header")):
+            if host[key][N] > side.capacity:
+                side._grow(int(host[key][N]))
+                grown = True
+        if grown:
+            vars(self).update(vars(pxd_match(self.signal, self.mixed)))
+            host = pxd_read_back(**self._columns())
+        total = int(host["header"][N])
+        cluster = host["cluster"][:total].copy()
+        image = host["first"][cluster] // np.int32(Hh * Ww)
+        out = {k: host[k][:total].copy() for k in self.PER_HIT}
+        match = host["lo"][cluster]
+        ok, k = match >= 0, np.maximum(match, 0)
+        of_match = lambda a: np.where(ok, a[k], 0).astype(a.dtype) if a.size else np.zeros(total, a.dtype)
+        return dict(out, cluster=cluster, sensor=(image % self.n_sensors).astype(np.int32), event=(image // self.n_sensors).astype(np.int32),
+                    du_mm=out["du"].astype(np.float64) * self.geometry.unit_mm, dv_mm=out["dv"].astype(np.float64) * self.geometry.unit_mm,
+                    match=match, counts=host["header"][:N].copy(), **{k: host[k][cluster] for k in ("found", "hi", "size", "charge")},
+                    **{k: of_match(host[k]) for k in ("mixed_charge", "signal_charge", "signal_size", "n_signal")})
+
+
+def pxd_match(signal, mixed):
+    """What became of every signal hit once background was laid over it (csrc/pxd_match.hip).  ``signal`` and ``mixed`` are the ``PXDHits``
+    of two batches of the same ``[N, H, W]``, made with the same sensors, threshold, cuts, ``head_tail`` and geometry on one device; in the
+    intended use ``mixed`` comes from the signal events with background laid over them (``PXDEventStore.overlay``), but the rule holds
+    for any two batches.  The join is pixel identity, in integers: a signal digit is *found* when its flat index is a mixed digit, ``L`` is
+    then that digit's mixed cluster.
+
+    * per signal cluster ``found`` (its found digits) and ``lo`` / ``hi`` (smallest / largest ``L``, -1 when nothing was found); ``lo`` is
+      the match.  For a true overlay ``found == size`` and ``lo == hi``: a connected set stays connected in a superset;
+    * per mixed cluster ``signal_size`` / ``signal_charge`` (number and summed signal charge of the signal digits found in it, at most the
+      mixed charge) and ``n_signal`` (signal clusters matched to it);
+    * per signal hit ``mixed_hit`` (row of the mixed hit of the matched cluster, or -1), ``flags`` -- ``PXD_MATCHED``: every digit found in
+      one mixed cluster that is itself a hit; ``PXD_CHANGED``: matched, and the mixed cluster's size or charge differs; ``PXD_SHARED``:
+      ``n_signal >= 2`` -- and ``du`` / ``dv`` = ``float32(float64(x_mixed) - float64(x_signal))`` in geometry units, 0 when not matched
+      and exactly 0 when matched and unchanged.
+
+    Integer atomics only: bit-identical run to run.  Launches on the current stream, neither synchronises nor copies, and can be captured
+    into a HIP graph.  When a side's digit total exceeds its capacity the device result covers the digits that fit; ``PXDMatch.cpu()``
+    reruns instead of handing back a truncated event.  Track-level quantities, time windows and a match by anything other than pixel
+    identity are out of scope.  ``ValueError`` when the two sides differ in shape, sensors, threshold, cuts, ``head_tail``, geometry or device."""
+    _check_match_sides(signal, mixed)
+    H.require_gpu()
+    s, m = signal, mixed
+    sp, sc, sd = s.positions, s.positions.clusters, s.positions.clusters.digits
+    mp, mc, md = m.positions, m.positions.clusters, m.positions.clusters.digits
+    (N, Hh, Ww), dev, Cs, Cm = s.shape, s.header.device, s.capacity, m.capacity
+    new = lambda n, dtype=torch.int32: torch.empty(n, dtype=dtype, device=dev)
+    out = dict({k: new(Cs) for k in PXDMatch.PER_SIGNAL_CLUSTER}, **{k: new(Cm) for k in PXDMatch.PER_MIXED_CLUSTER}, mixed_hit=new(Cs),
+               flags=new(Cs, torch.uint8), du=new(Cs, torch.float32), dv=new(Cs, torch.float32))
+    scratch = new(H.lib().ieagan_pxd_match_scratch(N, Hh, Ww, Cm))
+    with torch.cuda.device(dev):
+        H.call("ieagan_pxd_match", *_ptrs(Cs, sd.index, sd.charge, sc.label), sd.total.data_ptr(), *_ptrs(Cs, sc.size, sc.charge),
+               sc.total.data_ptr(), *_ptrs(Cs, sp.cluster), sp.total.data_ptr(), *_ptrs(Cs, s.u, s.v), *_ptrs(Cm, md.index, mc.label),
+               md.total.data_ptr(), *_ptrs(Cm, mc.size, mc.charge), mc.total.data_ptr(), *_ptrs(Cm, mp.cluster), mp.total.data_ptr(),
+               *_ptrs(Cm, m.u, m.v), N, Hh, Ww, Cs, Cm, *_ptrs(Cs, *(out[k] for k in PXDMatch.PER_SIGNAL_CLUSTER)),
+               *_ptrs(Cm, *(out[k] for k in PXDMatch.PER_MIXED_CLUSTER)), *_ptrs(Cs, *(out[k] for k in PXDMatch.PER_HIT)),
+               *_ptrs(Cm, scratch), H.stream())
+    return PXDMatch(s, m, **out)
+
+
+class PXDMatchStatistics(_PXDAccumulator):
+    """Accumulator of the per-sensor fate of the signal hits over batches, beside the other ``PXD*`` accumulators: ``update(signal_hits,
+    mixed_hits)`` runs ``pxd_match`` and ``ieagan_pxd_match_stats`` on the current stream, ``update(match)`` with an existing ``PXDMatch``
+    launches the statistics kernel alone; neither synchronises nor copies, ``result()`` does the single read-back.  Counters are exact
+    int64.  An update in which a side's digit total exceeds the capacity of its ``PXDHits`` is counted on the device and makes ``result()``
+    raise: a truncated event is never reported.  ``residual_bin``: the width of a residual bin in geometry units (default 10 = 5 um with the
+    default unit).  ``tables``: int64 ``[S * 165 + 1]`` on the device, the rows of the sensors, then the overflow counter."""
+    _table, _per_image, _overflow = "tables", ("hits",), False       # the overflow word is refused in result(), with this class's own text
+
+    def __init__(self, n_sensors=40, residual_bin=10, device=None):
+        self.residual_bin = int(residual_bin)
+        if self.residual_bin < 1:
+            raise ValueError(f"PXDMatchStatistics: residual_bin = {residual_bin} is not >= 1")
+        super().__init__(n_sensors, 0.0, None, device)
+        self.threshold, self.unit_mm = None, None          # the threshold is that of the hits, whatever it is
+
+    def update(self, signal_or_match, mixed=None):
+        if isinstance(signal_or_match, PXDMatch):
+            if mixed is not None:
+                raise TypeError("PXDMatchStatistics.update: a PXDMatch holds both sides, mixed= must be left out")
+            mt = signal_or_match
+        else:
+            _check_match_sides(signal_or_match, mixed, "PXDMatchStatistics.update")
+            mt = None
+        x = self._input(mt or signal_or_match, "PXDMatchStatistics.update", PXDMatch, PXDHits)
+        if self.unit_mm not in (None, x.geometry.unit_mm):
+            raise ValueError(f"PXDMatchStatistics.update: the geometry unit {x.geometry.unit_mm} mm differs from the accumulated {self.unit_mm}")
+        self.unit_mm = x.geometry.unit_mm
+        if mt is None:
+            mt = pxd_match(signal_or_match, mixed)
+        s, m, S = mt.signal, mt.mixed, self.n_sensors
+        sc, mc = s.positions.clusters, m.positions.clusters
+        (N, Hh, Ww), Cs, Cm = mt.shape, s.capacity, m.capacity
+        if self.tables is None:
+            self.tables = torch.zeros(S * H.PXD_MATCH_BINS + 1, dtype=torch.int64, device=self.device)
+        t = self.tables.data_ptr()
+        with torch.cuda.device(self.device):
+            H.call("ieagan_pxd_match_stats", *_ptrs(Cs, s.positions.cluster), s.total.data_ptr(), *_ptrs(Cs, sc.first), sc.total.data_ptr(),
+                   sc.digits.total.data_ptr(), *_ptrs(Cs, s.u, s.v), *_ptrs(Cm, mc.charge), mc.total.data_ptr(), m.total.data_ptr(),
+                   mc.digits.total.data_ptr(), *_ptrs(Cm, m.u, m.v), *_ptrs(Cs, mt.lo), *_ptrs(Cm, mt.signal_charge),
+                   *_ptrs(Cs, mt.mixed_hit, mt.flags), N, Hh, Ww, S, Cs, Cm, self.residual_bin, t, t + 8 * S * H.PXD_MATCH_BINS, H.stream())
+        self.hits.append(mt.counts)
+        return mt
+
+    def result(self):
+        """NumPy tables: int64 ``hits`` / ``matched`` / ``changed`` / ``shared`` / ``lost`` ``[S]`` by the sensor of the signal hit
+        (``shared``: matched hits whose mixed cluster holds two or more signal clusters; ``lost = hits - matched``); float64
+        ``efficiency = matched / hits``, ``changed_fraction`` and ``shared_fraction`` (of matched), NaN where the denominator is 0;
+        ``residual_u`` / ``residual_v [S, 64]`` over the matched and changed hits (bin ``clamp(floor(r / residual_bin) + 32, 0, 63)`` of
+        the float64 difference ``r`` in geometry units) and ``purity [S, 32]`` over the matched hits (bin ``min(32 * signal_charge //
+        mixed_charge, 31)``); ``residual_bin``, ``unit_mm``; ``hits_per_image`` int32 ``[events, S]`` and ``n_events``.  Raises when an
+        update overflowed."""
+        table, per_image = self._host_tables()
+        if table[-1] != 0:
+            raise RuntimeError(f"PXDMatchStatistics: {int(table[-1])} update(s) held more digits than the capacity of their PXDHits, their "
+                               "clusters are truncated: make the hits with a larger capacity=")
+        rows = table[:-1].reshape(self.n_sensors, H.PXD_MATCH_BINS)
+        out = {k: rows[:, i].copy() for i, k in enumerate(H.PXD_MATCH_COUNTERS)}
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out.update(efficiency=out["matched"] / out["hits"], changed_fraction=out["changed"] / out["matched"],
+                       shared_fraction=out["shared"] / out["matched"])
+        out.update((k, rows[:, a:a + n].copy()) for k, (a, n) in H.PXD_MATCH_COLUMNS.items())
+        return dict(out, residual_bin=self.residual_bin, unit_mm=self.unit_mm, hits_per_image=per_image["hits"], n_events=per_image["n_events"])
+
+
+def _pooled(result, num, den):
+    d = float(np.asarray(result[den]).sum())
+    return float(np.asarray(result[num]).sum()) / d if d > 0 else float("nan")
+
+
+def pxd_match_distance(real, fake):
+    """Six distances between two ``PXDMatchStatistics.result()`` tables -- the same signal under recorded and under generated background
+    -- (float64, host): ``efficiency_abs_err``, ``changed_abs_err``, ``shared_abs_err`` = absolute differences of the fractions pooled over
+    the sensors (matched / hits, changed / matched, shared / matched; NaN when a denominator is 0); ``residual_u_w1`` / ``residual_v_w1`` =
+    1-D Wasserstein distances in mm between the residual spectra and ``purity_w1`` (in units of purity, bins of 1 / 32), pooled over the
+    sensors and normalised to 1, NaN when one side is empty.  ``ValueError`` when the two sides differ in ``residual_bin`` or ``unit_mm``."""
+    for k in ("residual_bin", "unit_mm"):
+        if real[k] != fake[k]:
+            raise ValueError(f"pxd_match_distance: the two sides differ in {k}: {real[k]} and {fake[k]}")
+    out = {name: abs(_pooled(fake, num, den) - _pooled(real, num, den))
+           for name, num, den in (("efficiency_abs_err", "matched", "hits"), ("changed_abs_err", "changed", "matched"),
+                                  ("shared_abs_err", "shared", "matched"))}
+    width = float(real["residual_bin"]) * float(real["unit_mm"])
+    return dict(out, residual_u_w1=_w1(real["residual_u"], fake["residual_u"], width), residual_v_w1=_w1(real["residual_v"], fake["residual_v"], width),
+                purity_w1=_w1(real["purity"], fake["purity"], 1.0 / PXD_PURITY_BINS))

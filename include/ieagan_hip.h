@@ -565,6 +565,44 @@ int ieagan_pxd_event_overlay(const int* a_pos, const unsigned char* a_charge, co
                              int b_events, const int* b_ids, int E, int S, int H, int W, long capacity, int* out_pos,
                              unsigned char* out_charge, long* out_offsets, int* scratch, void* stream);
 
+/* ---- signal-hit matching under background: per-hit truth (pxd_match.hip) ----------------------------------
+ * Two ieagan_pxd_hits results over batches of the same [N, H, W] (s_*: signal, m_*: mixed, in the intended use the signal with background
+ * laid over it), each with its own capacity.  A signal digit is FOUND when its flat index occurs in the mixed digit list; L is then the
+ * mixed label of that digit.
+ *   per signal cluster j [s_capacity] int32   found = its found digits; lo / hi = smallest / largest L over them, both -1 when found == 0;
+ *                                             lo is the match
+ *   per mixed cluster k [m_capacity] int32    signal_size / signal_charge = number and summed SIGNAL charge of the signal digits found in
+ *                                             it; n_signal = signal clusters with lo == k
+ *   per signal hit h [s_capacity]             mixed_hit int32 = row of the mixed hit whose cluster is lo[s_cluster[h]], or -1;
+ *                                             flags uint8: bit 0 MATCHED (found == size, lo == hi >= 0, that mixed cluster is a hit),
+ *                                             bit 1 CHANGED (MATCHED, mixed size or charge differs), bit 2 SHARED (n_signal[lo] >= 2);
+ *                                             du / dv fp32 = (float)((double)m_u[mixed_hit] - (double)s_u[h]), 0 when not MATCHED
+ * Only the rows below the totals (read on the device, clipped to the capacities) are written.  Integer atomics only, no float is summed:
+ * two calls write the same bytes.  Memory safety does not depend on the content of the inputs: every total is clipped to its capacity, a
+ * label or cluster row is range-checked before it indexes anything, the search stays inside the clipped mixed list.  Four launches on
+ * `stream` whose shapes depend on the capacities alone, no synchronise, no copy (graph-capturable).
+ * scratch: ieagan_pxd_match_scratch(N, H, W, m_capacity) int32 words. */
+long ieagan_pxd_match_scratch(int N, int H, int W, long capacity);
+int ieagan_pxd_match(const int* s_index, const unsigned char* s_charge, const int* s_label, const int* s_digit_total, const int* s_size,
+                     const int* s_ccharge, const int* s_cluster_total, const int* s_cluster, const int* s_accepted_total, const float* s_u,
+                     const float* s_v, const int* m_index, const int* m_label, const int* m_digit_total, const int* m_size,
+                     const int* m_ccharge, const int* m_cluster_total, const int* m_cluster, const int* m_accepted_total, const float* m_u,
+                     const float* m_v, int N, int H, int W, long s_capacity, long m_capacity, int* found, int* lo, int* hi,
+                     int* signal_size, int* signal_charge, int* n_signal, int* mixed_hit, unsigned char* flags, float* du, float* dv,
+                     int* scratch, void* stream);
+/* Accumulates one ieagan_pxd_match result into table int64 [n_sensors * 165]; row of a sensor (that of the signal hit):
+ *   [0 .. 4]      hits, matched, changed, shared (MATCHED and SHARED), lost (not MATCHED)
+ *   [5 .. 68]     residual u, [69 .. 132] residual v, over the MATCHED and CHANGED hits: bin = clamp(floor(r / residual_bin) + 32, 0, 63),
+ *                 r = (double)m_u[mixed_hit] - (double)s_u[h], one IEEE division and a floor in float64
+ *   [133 .. 164]  purity over the MATCHED hits: min(32 * signal_charge[k] / m_ccharge[k], 31) in 64-bit integers, k = lo[s_cluster[h]]
+ * overflow [1] int64: + 1 when either side's digit total exceeds its capacity.  One launch, 64-bit integer atomics. */
+int ieagan_pxd_match_stats(const int* s_cluster, const int* s_accepted_total, const int* s_first, const int* s_cluster_total,
+                           const int* s_digit_total, const float* s_u, const float* s_v, const int* m_ccharge, const int* m_cluster_total,
+                           const int* m_accepted_total, const int* m_digit_total, const float* m_u, const float* m_v, const int* lo,
+                           const int* signal_charge, const int* mixed_hit, const unsigned char* flags, int N, int H, int W, int n_sensors,
+                           long s_capacity, long m_capacity, int residual_bin, unsigned long long* table, unsigned long long* overflow,
+                           void* stream);
+
 /* ---- orthogonal regularisation (ortho.hip) -------------------------------------------------------
  * Replaces utils.ortho (reference utils/__init__.py:843-859) for ALL weight matrices of a network in one call:
  * grad[l] += 2*strength * ((W_l W_l^T) (.) (1 - I)) W_l, fp32, on the flat parameter / gradient arenas.
