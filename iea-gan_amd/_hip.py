@@ -31,6 +31,7 @@ PXD_MAP_U, PXD_MAP_V = 25, 48       # bins of the ieagan_pxd_cluster_maps grid o
 PXD_MATCH_COUNTERS = ("hits", "matched", "changed", "shared", "lost")
 PXD_MATCH_COLUMNS = {"residual_u": (5, 64), "residual_v": (69, 64), "purity": (133, 32)}
 PXD_MATCH_BINS = 165
+PXD_CORR_MAX_COLUMNS, PXD_CORR_MAX_EVENTS = 1024, 65535      # csrc/pxd_corr.hip: columns R = S * RU * RV and events of a rank transform
 PROLOGUE_BWD_SLOTS = 64  # include/ieagan_hip.h: IEAGAN_PROLOGUE_BWD_SLOTS
 AUG_SLOTS = 128         # include/ieagan_hip.h: IEAGAN_AUG_SLOTS (per-image partial-sum slots of the DiffAugment entry points)
 BNB_REPL = 8            # replicas of the per-image accumulators of a BatchNorm-backward dgrad launch (common.h)
@@ -173,6 +174,9 @@ _SIGS = {
     "ieagan_pxd_match": [vp] * 21 + [i, i, i, l, l] + [vp] * 12,
     "ieagan_pxd_match_scratch": [i, i, i, l],
     "ieagan_pxd_match_stats": [vp] * 17 + [i, i, i, i, l, l, i] + [vp] * 3,
+    "ieagan_pxd_region_counts": [vp, vp, i, i, i, i, i, i, l, vp, vp, vp],
+    "ieagan_pxd_gram": [vp, i, i, vp, vp, vp],
+    "ieagan_pxd_ranks": [vp, i, i, vp, vp],
     "ieagan_ortho_ksplit": [],
     "ieagan_ortho_grad": [vp, vp, vp, vp, i, vp, i, vp, l, f, vp],
     "ieagan_selftest_tr_read": [vp, vp, vp],

@@ -1,4 +1,4 @@
-// What the kernels over PXD sensor images share (pxd_stats.hip, pxd_digits.hip, pxd_clusters.hip, pxd_reco.hip, pxd_hits.hip, pxd_events.hip, pxd_overlay.hip): the launch partition, the walk
+// What the kernels over PXD sensor images share (pxd_stats.hip, pxd_digits.hip, pxd_clusters.hip, pxd_reco.hip, pxd_hits.hip, pxd_events.hip, pxd_overlay.hip, pxd_match.hip, pxd_corr.hip): the launch partition, the walk
 // of a pixel range, the prefix sums, the row / column split and the launchers' argument checks.  Include after common.h.
 //
 // Launch partition: grid (P, N), workgroup (p, n) owns a contiguous pixel range of image n.

@@ -2,8 +2,9 @@
 (csrc/pxd_stats.hip), event production as sparse digits (csrc/pxd_digits.hip), clusters of the digits and their spectra
 (csrc/pxd_clusters.hip), cluster reconstruction -- cuts, charge-weighted positions, per-sensor position maps (csrc/pxd_reco.hip) --, hits in the local
 frame of a sensor with a geometry given as data (csrc/pxd_hits.hip), the event and hit files of ``produce.py`` and the store that keeps such a file's events on the device and expands them into the network input
-(csrc/pxd_events.hip), the overlay of the events of two stores, pixel by pixel in the sparse format (csrc/pxd_overlay.hip), and the match of
-the signal hits to the hits of the mixed events, hit by hit (csrc/pxd_match.hip).  ``utils`` re-exports every name defined here."""
+(csrc/pxd_events.hip), the overlay of the events of two stores, pixel by pixel in the sparse format (csrc/pxd_overlay.hip), the match of
+the signal hits to the hits of the mixed events, hit by hit (csrc/pxd_match.hip), and the correlations between the region occupancies of one
+event -- exact Pearson and Spearman tables from integer moments and ranks (csrc/pxd_corr.hip).  ``utils`` re-exports every name defined here."""
 from __future__ import annotations
 
 import numpy as np
@@ -90,7 +91,7 @@ class _PXDAccumulator:
         me, product = type(self).__name__, isinstance(given, products)
         x = given if product else _sensor_images(given, self.n_sensors, who, self.device)
         device = x.header.device if product else x.device
-        for k in ("n_sensors", "threshold", "seed_cut", "charge_cut", "device") if product else ():
+        for k in ("n_sensors", "threshold", "seed_cut", "charge_cut", "regions", "device") if product else ():
             made, mine = (device.index, self.device and self.device.index) if k == "device" else (getattr(x, k, None), getattr(self, k, None))
             if made != mine and None not in (made, mine):
                 raise ValueError(f"{me}.update: the {type(x).__name__} was made with {k} = {made}, not {mine}")
@@ -537,45 +538,200 @@ def pxd_map_distance(real, fake):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------
+# intra-event correlations: per-event region counts, their exact second moments and ranks (csrc/pxd_corr.hip)
+# ---------------------------------------------------------------------------------------------------------
+def _check_regions(who, regions, n_sensors, shape=None):
+    """``regions = (RU, RV)`` as two ints, after the bounds of the kernels: ``RU, RV >= 1``, ``n_sensors * RU * RV <= 1024`` and, once the
+    image size is known, ``RU <= H``, ``RV <= W``."""
+    try:
+        ru, rv = (int(v) for v in regions)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: regions must be a pair (RU, RV), got {regions!r}") from None
+    if ru < 1 or rv < 1:
+        raise ValueError(f"{who}: regions = {ru} x {rv} must be at least 1 x 1")
+    if int(n_sensors) * ru * rv > H.PXD_CORR_MAX_COLUMNS:
+        raise ValueError(f"{who}: {n_sensors} sensors x {ru} x {rv} regions are more than {H.PXD_CORR_MAX_COLUMNS} columns")
+    if shape is not None and (ru > shape[0] or rv > shape[1]):
+        raise ValueError(f"{who}: regions = {ru} x {rv} are finer than the {shape[0]} x {shape[1]} pixels of a sensor")
+    return ru, rv
+
+
+def _region_counts(d, regions, overflow):
+    """``ieagan_pxd_region_counts`` of a ``PXDDigits``: the int32 ``[E, R]`` table; ``overflow``: the device address of the int64 word."""
+    (N, Hh, Ww), S, (ru, rv), dev = d.shape, d.n_sensors, regions, d.index.device
+    x = torch.empty(N // S, S * ru * rv, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        H.call("ieagan_pxd_region_counts", *_ptrs(d.capacity, d.index), d.total.data_ptr(), N, Hh, Ww, S, ru, rv, d.capacity, x.data_ptr(),
+               overflow, H.stream())
+    return x
+
+
+def _gram(x, tables):
+    """``ieagan_pxd_gram``: the moments of the int32 table ``x [E, R]`` added into ``tables`` (int64, gram ``[R * R]`` then sum ``[R]``)."""
+    E, R = x.shape
+    with torch.cuda.device(x.device):
+        H.call("ieagan_pxd_gram", x.data_ptr(), E, R, tables.data_ptr(), tables.data_ptr() + 8 * R * R, H.stream())
+
+
+def pxd_region_counts(images_or_digits, regions=(1, 1), threshold=0.0, capacity=None, n_sensors=40):
+    """The per-event occupancy table of a batch, int32 ``[E, R]`` on the device (csrc/pxd_corr.hip): a grid of ``regions = (RU, RV)`` lies
+    over every sensor, a digit at row ``r``, column ``c`` of image ``n`` belongs to event ``n // S``, sensor ``s = n % S`` and region
+    ``ru = r * RU // H``, ``rv = c * RV // W`` (integers), and counts for column ``(s * RU + ru) * RV + rv`` of ``R = S * RU * RV <= 1024``.
+    Input: sensor images ``[N, H, W]`` (``pxd_digits(images, threshold, capacity, n_sensors)`` runs first) or an existing ``PXDDigits``
+    (its threshold, capacity and sensors hold).  ``(1, 1)`` counts whole sensors.  int32 atomics only: bit-identical run to run.
+
+    Launches on the current stream, neither synchronises nor copies.  When the digit total exceeds the capacity the table covers the
+    first ``capacity`` digits (``PXDDigits.total`` holds the true number); ``PXDCorrelations`` refuses such an update in ``result()``."""
+    H.require_gpu()
+    d = images_or_digits if isinstance(images_or_digits, PXDDigits) else pxd_digits(images_or_digits, threshold, capacity, n_sensors)
+    regions = _check_regions("pxd_region_counts", regions, d.n_sensors, d.shape[1:])
+    return _region_counts(d, regions, torch.zeros(1, dtype=torch.int64, device=d.index.device).data_ptr())
+
+
+def _correlation(n, gram, total):
+    """The coefficient table ``[R, R]`` float64 of the integer moments of ``n`` events: ``cov_ij = n * gram_ij - total_i * total_j`` and
+    ``var_i = cov_ii`` in exact integers (Python ``int``: ``n * gram`` can pass 2**63), ``rho_ij = float(cov_ij) / sqrt(float(var_i) *
+    float(var_j))``; NaN where a variance is 0 or ``n < 2``."""
+    g, s = np.asarray(gram).astype(object), np.asarray(total).astype(object)
+    cov = int(n) * g - np.outer(s, s)
+    var = np.array([float(v) for v in np.diagonal(cov)], np.float64)
+    ok = (var[:, None] != 0) & (var[None, :] != 0) & (int(n) >= 2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rho = cov.astype(np.float64) / np.sqrt(var[:, None] * var[None, :])
+    return np.where(ok, rho, np.nan)
+
+
+class PXDCorrelations(_PXDAccumulator):
+    """Accumulator of the correlations between the region occupancies of one event, over the events: what ties the 40 sensor images of
+    an event together (a busy event is busy on every sensor), which no per-sensor statistic sees.  ``regions = (RU, RV)``: the grid over a
+    sensor, ``R = n_sensors * RU * RV <= 1024`` columns (``pxd_region_counts``); ``(1, 1)`` is the sensor-level matrix.  ``update`` takes
+    images, the ``PXDDigits`` of the batch or its ``PXDClusters`` (their digits) and launches ``ieagan_pxd_region_counts`` and
+    ``ieagan_pxd_gram`` on the current stream; it keeps the batch's table ``[E, R]`` on the device and neither synchronises nor copies.
+    ``result()`` ranks the columns of the whole table (``ieagan_pxd_ranks``, at most 65535 events), takes the moments of the ranks and
+    does the single read-back.  Every device number is an exact integer; the host does the float64 arithmetic on the tables.  ``capacity``
+    (digits per update) defaults to that of ``pxd_digits``; an update whose digit total exceeds it is counted on the device and makes
+    ``result()`` raise.  ``tables``: int64 ``[R * R + R + 1]`` on the device, gram, sum, then the overflow counter."""
+    _per_image = ("counts", "rank_tables")          # rank_tables: the one int64 table of the ranks' moments, made by result()
+
+    def __init__(self, n_sensors=40, threshold=7.0, regions=(1, 1), capacity=None, device=None):
+        self.regions = _check_regions("PXDCorrelations", regions, n_sensors)
+        super().__init__(n_sensors, threshold, capacity, device)
+
+    def update(self, images_or_product):
+        d = self._input(images_or_product, "pxd_digits", PXDDigits, PXDClusters)        # a wrong dtype or rank is reported as by pxd_digits
+        if isinstance(d, PXDClusters):
+            d = d.digits
+        elif not isinstance(d, PXDDigits):
+            d = pxd_digits(d, self.threshold, self.capacity, self.n_sensors)
+        _check_regions("PXDCorrelations.update", self.regions, self.n_sensors, self.shape)
+        R = self.n_sensors * self.regions[0] * self.regions[1]
+        if self.tables is None:
+            self.tables = torch.zeros(R * R + R + 1, dtype=torch.int64, device=self.device)
+        x = _region_counts(d, self.regions, self.tables.data_ptr() + 8 * (R * R + R))
+        _gram(x, self.tables)
+        self.counts.append(x)
+        return x
+
+    def result(self):
+        """NumPy tables.  Integers: ``gram`` int64 ``[R, R]`` (sum over the events of ``x_i * x_j``, symmetric) and ``sum`` int64 ``[R]`` of
+        the counts, ``rank_gram`` / ``rank_sum`` the same of ``rank2 = 2 * #{smaller} + #{equal} + 1`` (twice the mid-rank of a count among
+        the events, ``2 * scipy.stats.rankdata``), ``counts`` int32 ``[events, R]``, ``n_events``, ``regions`` and ``shape`` (the image size).
+        Float64 ``[R, R]``: ``pearson`` from ``(sum, gram)`` and ``spearman`` from ``(rank_sum, rank_gram)`` by ``cov_ij = n * G_ij - s_i *
+        s_j`` in exact integers and ``float(cov_ij) / sqrt(float(var_i) * float(var_j))``; NaN where a column never varies or with fewer
+        than 2 events.  Raises when an update overflowed, before any update and beyond 65535 events."""
+        who = type(self).__name__
+        if not self.counts:
+            raise RuntimeError(f"{who}.result() before any update()")
+        x = self.counts[0] if len(self.counts) == 1 else torch.cat(self.counts)
+        E, R = x.shape
+        if E > H.PXD_CORR_MAX_EVENTS:
+            raise ValueError(f"{who}.result: {E} events are more than the {H.PXD_CORR_MAX_EVENTS} the rank transform takes")
+        rank2, moments = torch.empty_like(x), torch.zeros(R * R + R, dtype=torch.int64, device=x.device)
+        with torch.cuda.device(x.device):
+            H.call("ieagan_pxd_ranks", x.data_ptr(), E, R, rank2.data_ptr(), H.stream())
+        _gram(rank2, moments)
+        self.counts, self.rank_tables = [x], [moments]
+        table, host = self._host_tables()           # the one read-back; refuses an overflow
+        ranks, counts = host["rank_tables"].reshape(-1), host["counts"].reshape(E, R)
+        gram, total = table[:R * R].reshape(R, R), table[R * R:]
+        rank_gram, rank_sum = ranks[:R * R].reshape(R, R), ranks[R * R:]
+        return dict(gram=gram, sum=total, rank_gram=rank_gram, rank_sum=rank_sum, counts=counts, n_events=E, regions=self.regions,
+                    shape=self.shape, pearson=_correlation(E, gram, total), spearman=_correlation(E, rank_gram, rank_sum))
+
+
+def pxd_correlation_distance(real, fake):
+    """Four distances between two ``PXDCorrelations.result()`` tables (float64, host), over the pairs ``i < j`` whose real coefficient is
+    defined (a fake NaN counts as 0): ``pearson_rms`` / ``spearman_rms`` = root mean square of ``rho_fake - rho_real``;
+    ``spearman_max_abs`` = the largest such difference; ``spearman_strength_err`` = mean ``|rho_fake|`` minus mean ``|rho_real|`` (negative:
+    the generator under-correlates).  NaN when no pair is defined.  ``ValueError`` when ``regions``, the columns or ``shape`` differ."""
+    for k in ("regions", "shape"):
+        if tuple(real[k]) != tuple(fake[k]):
+            raise ValueError(f"pxd_correlation_distance: the two sides differ in {k}: {real[k]} and {fake[k]}")
+    if np.shape(real["spearman"]) != np.shape(fake["spearman"]):
+        raise ValueError(f"pxd_correlation_distance: the two sides differ in columns: {np.shape(real['spearman'])[0]} and {np.shape(fake['spearman'])[0]}")
+    upper = np.triu(np.ones(np.shape(real["spearman"]), bool), 1)
+
+    def pairs(name):            # the real and the fake coefficient of every pair that counts
+        r = np.asarray(real[name], np.float64)
+        ok = upper & ~np.isnan(r)
+        return r[ok], np.nan_to_num(np.asarray(fake[name], np.float64), nan=0.0)[ok]
+    (pr, pf), (sr, sf) = pairs("pearson"), pairs("spearman")
+    rms = lambda r, f: float(np.sqrt(np.mean((f - r) ** 2))) if r.size else float("nan")
+    return dict(pearson_rms=rms(pr, pf), spearman_rms=rms(sr, sf),
+                spearman_max_abs=float(np.abs(sf - sr).max()) if sr.size else float("nan"),
+                spearman_strength_err=float(np.abs(sf).mean() - np.abs(sr).mean()) if sr.size else float("nan"))
+
+
 class PXDValidation:
     """The accumulators of one side of a validation, fed together: ``stats`` (a ``PXDStatistics``), ``clusters`` (a ``PXDClusterStatistics``
-    with ``clusters=True``, else None) and ``maps`` (a ``PXDClusterMaps`` without cuts with ``maps=True``, with the cuts of ``maps=(seed_cut,
-    charge_cut)``, else None); ``n_sensors``, ``threshold``, ``device`` and, where there is one, ``capacity`` go to each.  ``update`` runs the
-    chain once -- digits, clusters, positions -- and hands each accumulator the product before it; like the parts it neither synchronises
-    nor copies."""
+    with ``clusters=True``, else None), ``maps`` (a ``PXDClusterMaps`` without cuts with ``maps=True``, with the cuts of ``maps=(seed_cut,
+    charge_cut)``, else None) and ``correlations`` (a ``PXDCorrelations`` of whole sensors with ``correlations=True``, on the grid of
+    ``correlations=(RU, RV)``, else None); ``n_sensors``, ``threshold``, ``device`` and, where there is one, ``capacity`` go to each.
+    ``update`` runs the chain once -- digits, clusters, positions -- and hands each accumulator the product before it (the correlations
+    run ``pxd_digits`` alone when the chain is off); like the parts it neither synchronises nor copies."""
 
-    def __init__(self, clusters=False, maps=False, capacity=None, **kw):
+    def __init__(self, clusters=False, maps=False, capacity=None, correlations=False, **kw):
         self.capacity, self.stats = capacity, PXDStatistics(**kw)
         self.clusters = PXDClusterStatistics(capacity=capacity, **kw) if clusters else None
         seed_cut, charge_cut = maps if isinstance(maps, (tuple, list)) else (0, 0)
         self.maps = PXDClusterMaps(seed_cut=seed_cut, charge_cut=charge_cut, capacity=capacity, **kw) if maps not in (False, None) else None
+        regions = correlations if isinstance(correlations, (tuple, list)) else (1, 1)
+        self.correlations = PXDCorrelations(regions=regions, capacity=capacity, **kw) if correlations not in (False, None) else None
 
     def update(self, images):
         x = _sensor_images(images, self.stats.n_sensors, "PXDValidation.update", self.stats.device)
         self.stats.update(x)
         if self.clusters is not None or self.maps is not None:
             c = pxd_clusters(x, self.stats.threshold, self.capacity, self.stats.n_sensors)
-            for acc in filter(None, (self.clusters, self.maps)):
+            for acc in filter(None, (self.clusters, self.maps, self.correlations)):
                 acc.update(c)
+        elif self.correlations is not None:
+            self.correlations.update(x)
 
     def result(self):
-        """``{"stats": ..., "clusters": ..., "maps": ...}``: the ``result()`` of every accumulator that is on."""
+        """``{"stats": ..., "clusters": ..., "maps": ..., "correlations": ...}``: the ``result()`` of every accumulator that is on."""
         return {part: getattr(self, part).result() for part, _, _ in _PARTS if getattr(self, part) is not None}
 
 
 # the parts of a PXDValidation.result(): name, distance function, and the keys that are no table of their own beside the statistics'
-_PARTS = (("stats", pxd_distance, ()), ("clusters", pxd_cluster_distance, ("n_events",)), ("maps", pxd_map_distance, ("n_events", "shape")))
+_PARTS = (("stats", pxd_distance, ()), ("clusters", pxd_cluster_distance, ("n_events",)), ("maps", pxd_map_distance, ("n_events", "shape")),
+          ("correlations", pxd_correlation_distance, ("n_events", "shape", "regions")))
+# the tables of a part that would share a name with another part's: their name in pxd_validation_tables
+_TABLE_NAMES = {("maps", "clusters"): "accepted_clusters", ("correlations", "counts"): "region_counts"}
 
 
 def pxd_validation_distance(real, fake):
-    """``pxd_distance``, ``pxd_cluster_distance`` and ``pxd_map_distance`` of the parts both ``PXDValidation.result()`` have, in one dict."""
+    """``pxd_distance``, ``pxd_cluster_distance``, ``pxd_map_distance`` and ``pxd_correlation_distance`` of the parts both
+    ``PXDValidation.result()`` have, in one dict."""
     return {k: v for part, distance, _ in _PARTS if part in real and part in fake for k, v in distance(real[part], fake[part]).items()}
 
 
 def pxd_validation_tables(**sides):
     """``pxd_validation_tables(real=r, fake=f)``: every table of each side's ``PXDValidation.result()`` as ``<side>_<name>``, part by part;
-    the per-image ``clusters`` of the maps are ``<side>_accepted_clusters``, beside the cluster statistics' ``<side>_clusters``."""
-    return {f"{side}_{'accepted_clusters' if (part, k) == ('maps', 'clusters') else k}": np.asarray(v) for part, _, skip in _PARTS
+    the per-image ``clusters`` of the maps are ``<side>_accepted_clusters``, beside the cluster statistics' ``<side>_clusters``, and the
+    per-event ``counts`` of the correlations are ``<side>_region_counts``."""
+    return {f"{side}_{_TABLE_NAMES.get((part, k), k)}": np.asarray(v) for part, _, skip in _PARTS
             for side, res in sides.items() for k, v in res.get(part, {}).items() if k not in skip}
 
 

@@ -100,15 +100,16 @@ def test(G, D, G_ema, state_dict, config, test_log):
     test_log.log(itr=int(state_dict["itr"]), FID=float(FID))
 
 
-def generated_statistics(net, config, n_events, clusters=False, maps=False):
+def generated_statistics(net, config, n_events, clusters=False, maps=False, correlations=False):
     """A ``utils.PXDValidation`` over ``n_events`` events generated by ``net`` (eval mode when ``G_eval_mode``, no_grad, export epilogue):
     its ``.stats``, with ``clusters=True`` its ``.clusters`` and with ``maps=True`` or ``maps=(seed_cut, charge_cut)`` (ADU) its ``.maps``
-    are fed.  The latents and ``rdof`` come from a ``torch.Generator`` of its own seeded with ``config['seed']``: the global generators
+    and with ``correlations=True`` or ``correlations=(RU, RV)`` its ``.correlations`` are fed.  The latents and ``rdof`` come from a
+    ``torch.Generator`` of its own seeded with ``config['seed']``: the global generators
     are not touched; the ``.training`` flags are restored.  No host synchronisation."""
     dev = next(net.parameters()).device
     n = int(config["n_classes"])
     gen = torch.Generator(device=dev).manual_seed(int(config["seed"]))
-    acc = utils.PXDValidation(clusters, maps, n_sensors=n, threshold=float(config["val_threshold"]), device=dev)
+    acc = utils.PXDValidation(clusters, maps, correlations=correlations, n_sensors=n, threshold=float(config["val_threshold"]), device=dev)
     y = torch.arange(n, dtype=torch.long, device=dev)
     was_training = net.training
     if config["G_eval_mode"]:

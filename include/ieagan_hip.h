@@ -603,6 +603,29 @@ int ieagan_pxd_match_stats(const int* s_cluster, const int* s_accepted_total, co
                            long s_capacity, long m_capacity, int residual_bin, unsigned long long* table, unsigned long long* overflow,
                            void* stream);
 
+/* ---- intra-event correlations: region counts, their moments and ranks (pxd_corr.hip) -----------------------
+ * A grid of RU x RV regions lies over every sensor (1 <= RU <= H, 1 <= RV <= W).  A digit at row r, column c of image n belongs to event
+ * e = n / n_sensors, sensor s = n % n_sensors, region ru = (r * RU) / H, rv = (c * RV) / W in integers, and counts for column
+ * k = (s * RU + ru) * RV + rv of R = n_sensors * RU * RV <= 1024 columns.  Input: the ascending digit list of one ieagan_pxd_digits result
+ * (index [capacity], digit_total read on the device; N a multiple of n_sensors, E = N / n_sensors events).
+ *   x [E * R] int32     x[e * R + k] = the digits of event e in column k among the first min(*digit_total, capacity); zeroed by the call
+ *   overflow [1] int64  + 1 when *digit_total > capacity, i.e. when the counts come from a truncated digit list
+ * int32 atomics only: two calls write the same bytes.  The total is clipped to [0, capacity] and a digit whose flat index is outside
+ * [0, N * H * W) is skipped: a list that breaks its contract gives wrong counts, never a wrong address.  Two launches on `stream` whose
+ * shapes depend on (N, n_sensors, RU, RV, capacity) alone, no synchronise, no copy (graph-capturable; capacity 0: index may be NULL). */
+int ieagan_pxd_region_counts(const int* index, const int* digit_total, int N, int H, int W, int n_sensors, int RU, int RV, long capacity,
+                             int* x, unsigned long long* overflow, void* stream);
+/* Second moments of any int32 table x [E, R] (1 <= E <= 65535, 1 <= R <= 1024), ACCUMULATED across calls (the caller zeroes them once):
+ * gram [R * R] int64 += x^T x, the full symmetric table, and sum [R] int64 += the column sums.  One thread owns each entry (a plain 64-bit
+ * read-modify-write, no atomics; successive calls are ordered by the stream) and both triangles are computed: gram equals its transpose
+ * bit for bit.  Exact as long as the true sums fit int64 (counts x <= H * W: below 2^63 / (H * W)^2 events).  One launch. */
+int ieagan_pxd_gram(const int* x, int E, int R, long long* gram, long long* sum, void* stream);
+/* Rank transform of the columns of x [E, R] int32 (1 <= E <= 65535, 1 <= R <= 1024) into rank2 [E, R] int32 (not x itself):
+ *   rank2[e, k] = 2 * #{e' : x[e', k] < x[e, k]} + #{e' : x[e', k] == x[e, k]} + 1 <= 2 E + 1
+ * twice the mid-rank of the entry in its column (ties share the average rank), an integer.  E * E * R compares, one writer per entry, no
+ * atomics; tiles at the edges are predicated, nothing is read or written out of range.  One launch. */
+int ieagan_pxd_ranks(const int* x, int E, int R, int* rank2, void* stream);
+
 /* ---- orthogonal regularisation (ortho.hip) -------------------------------------------------------
  * Replaces utils.ortho (reference utils/__init__.py:843-859) for ALL weight matrices of a network in one call:
  * grad[l] += 2*strength * ((W_l W_l^T) (.) (1 - I)) W_l, fp32, on the flat parameter / gradient arenas.
