@@ -18,7 +18,7 @@
 //   flatten  wave g owns the digits [g * chunk, (g + 1) * chunk): parent[k] = find(k).  Smaller roots absorb larger ones, so the root of a
 //            cluster is its first digit whatever the schedule was.  Every digit adds into its root's slots with integer atomics (add, min,
 //            max: order-independent, exact), and the wave stores the number of roots among its digits into its own slot.
-//   scan     one workgroup: exclusive prefix sum over the wave slots (ascending k), in place; writes total.
+//   scan     one workgroup: exclusive prefix sum over the wave slots (ascending k), in place; writes total (pxd_scan_total_kernel).
 //   compact  the partition of flatten: rank of root k = base[slot] + roots of the wave's earlier steps + roots in the lower lanes (ballot).
 //            Writes the cluster table at the rank and rank[k].  No atomic decides a position.
 //   label    label[k] = rank[parent[k]];  counts[n] = clusters whose first digit lies in image n (two lower_bounds over `first`).
@@ -66,8 +66,8 @@ __device__ __forceinline__ void cl_union(int* parent, int a, int b) {
 
 __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_init_kernel(const int* __restrict__ dtotal, int cap, int* __restrict__ parent,
                                                                         int* __restrict__ acc) {
-    const int M = min(dtotal[0], cap);
-    for (int k = blockIdx.x * PXD_THREADS + threadIdx.x; k < M; k += gridDim.x * PXD_THREADS) {
+    const int M = pxd_total(dtotal, cap);
+    for (int k = pxd_grid_thread(); k < M; k += pxd_grid_threads()) {
         parent[k] = k;
         acc[k] = 0;
         acc[(long)cap + k] = 0;
@@ -81,8 +81,8 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_init_kernel(const in
 
 __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_link_kernel(const int* __restrict__ index, const int* __restrict__ dtotal, int cap,
                                                                         int HW, int W, int* parent) {
-    const int M = min(dtotal[0], cap);
-    for (int k = blockIdx.x * PXD_THREADS + threadIdx.x; k < M; k += gridDim.x * PXD_THREADS) {
+    const int M = pxd_total(dtotal, cap);
+    for (int k = pxd_grid_thread(); k < M; k += pxd_grid_threads()) {
         const int idx = index[k];
         int r, c;
         pxd_row_col(idx, HW, W, r, c);
@@ -102,12 +102,9 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_link_kernel(const in
 __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_flatten_kernel(const int* __restrict__ index, const uint8_t* __restrict__ charge,
                                                                            const int* __restrict__ dtotal, int cap, int chunk, int HW, int W,
                                                                            int* parent, int* acc, int* __restrict__ slots) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
-    const long M = min(dtotal[0], cap);
-    const long k0 = (long)g * chunk;
-    const long k1 = k0 + chunk < M ? k0 + chunk : M;
+    const PxdWaveRange w(pxd_total(dtotal, cap), chunk);
     int roots = 0;
-    for (long kk = k0 + lane; kk < k1; kk += 64) {
+    for (long kk = w.k0 + w.lane; kk < w.k1; kk += 64) {
         const int k = (int)kk;
         const int root = cl_find(parent, k);
         __hip_atomic_store(parent + k, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -123,15 +120,8 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_flatten_kernel(const
         atomicMin(acc + 5L * cap + root, c);
         atomicMax(acc + 6L * cap + root, c);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) roots += __shfl_xor(roots, o, 64);
-    if (lane == 0) slots[g] = roots;
-}
-
-// The prefix sum of pxd_common.h over the wave slots of the flatten launch (groups <= CL_MAX_BLOCKS: one tile); writes total.
-__global__ __launch_bounds__(PXD_SCAN_THREADS) void pxd_clusters_scan_kernel(int* __restrict__ slots, int groups, int* __restrict__ total) {
-    const int all = pxd_scan_slots(slots, groups);
-    if (threadIdx.x == 0) total[0] = all;
+    roots = pxd_wave_sum(roots);
+    if (w.lane == 0) slots[w.g] = roots;
 }
 
 __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_compact_kernel(const int* __restrict__ index, const int* __restrict__ dtotal, int cap,
@@ -140,19 +130,16 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_compact_kernel(const
                                                                            int* __restrict__ first, int* __restrict__ size, int* __restrict__ ccharge,
                                                                            uint8_t* __restrict__ seed, int* __restrict__ size_u,
                                                                            int* __restrict__ size_v) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
-    const long M = min(dtotal[0], cap);
-    const long k0 = (long)g * chunk;
-    const long k1 = k0 + chunk < M ? k0 + chunk : M;
-    int run = slots[g];
-    for (long kb = k0; kb < k1; kb += 64) {         // wave-uniform bounds
-        const long kk = kb + lane;
+    const PxdWaveRange w(pxd_total(dtotal, cap), chunk);
+    int run = slots[w.g];
+    for (long kb = w.k0; kb < w.k1; kb += 64) {
+        const long kk = kb + w.lane;
         const int k = (int)kk;
-        const bool is_root = kk < k1 && parent[k] == k;
+        const bool is_root = kk < w.k1 && parent[k] == k;
         const unsigned long long m = __ballot(is_root);
         if (m == 0ull) continue;
         if (is_root) {                              // clusters <= digits <= capacity: the rank is inside every table
-            const int j = run + __popcll(m & ((1ull << lane) - 1ull));
+            const int j = run + pxd_ballot_rank(m, w.lane);
             rank[k] = j;
             first[j] = index[k];
             size[j] = acc[k];
@@ -169,11 +156,9 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_clusters_label_kernel(const i
                                                                          const int* __restrict__ rank, const int* __restrict__ first,
                                                                          const int* __restrict__ total, int N, int HW, int* __restrict__ label,
                                                                          int* __restrict__ counts) {
-    const int M = min(dtotal[0], cap);
-    const int t0 = blockIdx.x * PXD_THREADS + threadIdx.x;
-    for (int k = t0; k < M; k += gridDim.x * PXD_THREADS) label[k] = rank[parent[k]];
-    const int T = total[0];
-    for (int n = t0; n < N; n += gridDim.x * PXD_THREADS)       // (n + 1) * HW <= N * HW < 2^31
+    const int M = pxd_total(dtotal, cap), T = pxd_total(total, cap);
+    for (int k = pxd_grid_thread(); k < M; k += pxd_grid_threads()) label[k] = rank[parent[k]];
+    for (int n = pxd_grid_thread(); n < N; n += pxd_grid_threads())         // (n + 1) * HW <= N * HW < 2^31
         counts[n] = cl_lower_bound(first, T, (n + 1) * HW) - cl_lower_bound(first, T, n * HW);
 }
 
@@ -183,10 +168,10 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_cluster_stats_kernel(const in
                                                                         const int* __restrict__ ctotal, const int* __restrict__ dtotal, int cap, int HW,
                                                                         int n_sensors, unsigned long long* __restrict__ tables,
                                                                         unsigned long long* __restrict__ overflow) {
-    const int t0 = blockIdx.x * PXD_THREADS + threadIdx.x;
+    const int t0 = pxd_grid_thread();
     if (t0 == 0 && dtotal[0] > cap) atomicAdd(overflow, 1ull);
-    const int T = min(ctotal[0], cap);
-    for (int j = t0; j < T; j += gridDim.x * PXD_THREADS) {
+    const int T = pxd_total(ctotal, cap);
+    for (int j = t0; j < T; j += pxd_grid_threads()) {
         unsigned long long* row = tables + (long)((first[j] / HW) % n_sensors) * CL_COLUMNS;
         atomicAdd(row + min(size[j], CL_SIZE_BINS) - 1, 1ull);
         atomicAdd(row + CL_SIZE_BINS + min(ccharge[j] >> 3, CL_CHARGE_BINS - 1), 1ull);
@@ -206,20 +191,16 @@ extern "C" int ieagan_pxd_clusters(const int* index, const unsigned char* charge
                                    int* label, int* first, int* size, int* ccharge, unsigned char* seed, int* size_u, int* size_v, int* counts,
                                    int* total, int* scratch, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = pxd_check_geometry("pxd_clusters", N, H, W, true)) return rc;
-    CHECK_ARG((double)H * W * 255.0 < 2147483648.0, "pxd_clusters: H * W * 255 = %d * %d * 255 does not fit the int32 cluster charge", H, W);
-    CHECK_ARG(capacity >= 0, "pxd_clusters: capacity = %ld is negative", capacity);
-    CHECK_ARG(digit_total != nullptr && ((uintptr_t)digit_total & 3u) == 0, "pxd_clusters: digit_total is NULL or misaligned");
-    CHECK_ARG(capacity == 0 || (index != nullptr && charge != nullptr), "pxd_clusters: index / charge is NULL with capacity %ld", capacity);
-    CHECK_ARG(capacity == 0 || (label != nullptr && first != nullptr && size != nullptr && ccharge != nullptr && seed != nullptr &&
-                                size_u != nullptr && size_v != nullptr),
-              "pxd_clusters: an output table is NULL with capacity %ld", capacity);
-    CHECK_ARG((((uintptr_t)index | (uintptr_t)label | (uintptr_t)first | (uintptr_t)size | (uintptr_t)ccharge | (uintptr_t)size_u |
-                (uintptr_t)size_v) & 3u) == 0, "pxd_clusters: an int32 array is not 4-byte aligned");
-    CHECK_ARG(counts != nullptr && total != nullptr && (((uintptr_t)counts | (uintptr_t)total) & 3u) == 0,
-              "pxd_clusters: counts / total is NULL or misaligned");
-    CHECK_ARG(scratch != nullptr && ((uintptr_t)scratch & 3u) == 0,
-              "pxd_clusters: scratch (ieagan_pxd_clusters_scratch int32 words) is NULL or misaligned");
+    const char* who = "pxd_clusters";
+    if (int rc = pxd_check_geometry(who, N, H, W, true)) return rc;
+    if (int rc = pxd_check_cluster_charge(who, H, W)) return rc;
+    if (int rc = pxd_check_capacity(who, "capacity", capacity)) return rc;
+    if (int rc = pxd_check_totals(who, "digit_total", {digit_total})) return rc;
+    if (int rc = pxd_check_arrays(who, "index / charge", "capacity", capacity, {index, charge})) return rc;
+    if (int rc = pxd_check_arrays(who, "an output table", "capacity", capacity, {label, first, size, ccharge, seed, size_u, size_v})) return rc;
+    if (int rc = pxd_check_aligned(who, "an int32 array", 4, {index, label, first, size, ccharge, size_u, size_v})) return rc;
+    if (int rc = pxd_check_needed(who, "counts / total", 4, {counts, total})) return rc;
+    if (int rc = pxd_check_needed(who, "scratch (ieagan_pxd_clusters_scratch int32 words)", 4, {scratch})) return rc;
     const int cap = pxd_cap(capacity);
     const int HW = H * W;
     const int B = cl_blocks(cap), chunk = cl_chunk(cap, B);
@@ -227,7 +208,7 @@ extern "C" int ieagan_pxd_clusters(const int* index, const unsigned char* charge
     int* rank = scratch + (long)cap;
     int* acc = scratch + 2L * cap;
     int* slots = scratch + (2L + CL_ACC) * cap;
-    ProfScope prof("pxd_clusters", 0.0, 0.0, st);
+    ProfScope prof(who, 0.0, 0.0, st);
     hipLaunchKernelGGL(pxd_clusters_init_kernel, dim3(B), dim3(PXD_THREADS), 0, st, digit_total, cap, parent, acc);
     CHECK_LAUNCH("pxd_clusters init");
     hipLaunchKernelGGL(pxd_clusters_link_kernel, dim3(B), dim3(PXD_THREADS), 0, st, index, digit_total, cap, HW, W, parent);
@@ -235,7 +216,7 @@ extern "C" int ieagan_pxd_clusters(const int* index, const unsigned char* charge
     hipLaunchKernelGGL(pxd_clusters_flatten_kernel, dim3(B), dim3(PXD_THREADS), 0, st, index, (const uint8_t*)charge, digit_total, cap, chunk, HW, W,
                        parent, acc, slots);
     CHECK_LAUNCH("pxd_clusters flatten");
-    hipLaunchKernelGGL(pxd_clusters_scan_kernel, dim3(1), dim3(PXD_SCAN_THREADS), 0, st, slots, B, total);
+    hipLaunchKernelGGL(pxd_scan_total_kernel<PXD_SCAN_THREADS>, dim3(1), dim3(PXD_SCAN_THREADS), 0, st, slots, B, total);
     CHECK_LAUNCH("pxd_clusters scan");
     hipLaunchKernelGGL(pxd_clusters_compact_kernel, dim3(B), dim3(PXD_THREADS), 0, st, index, digit_total, cap, chunk, (const int*)parent,
                        (const int*)acc, (const int*)slots, rank, first, size, ccharge, (uint8_t*)seed, size_u, size_v);
@@ -250,16 +231,15 @@ extern "C" int ieagan_pxd_cluster_stats(const int* first, const int* size, const
                                         const int* size_v, const int* cluster_total, const int* digit_total, int N, int H, int W, int n_sensors,
                                         long capacity, unsigned long long* tables, unsigned long long* overflow, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = pxd_check_geometry("pxd_cluster_stats", N, H, W, true)) return rc;
-    CHECK_ARG(n_sensors > 0 && N % n_sensors == 0, "pxd_cluster_stats: N = %d is not a multiple of n_sensors = %d", N, n_sensors);
-    CHECK_ARG(capacity >= 0, "pxd_cluster_stats: capacity = %ld is negative", capacity);
-    CHECK_ARG(capacity == 0 || (first != nullptr && size != nullptr && ccharge != nullptr && seed != nullptr && size_u != nullptr &&
-                                size_v != nullptr), "pxd_cluster_stats: a cluster table is NULL with capacity %ld", capacity);
-    CHECK_ARG(cluster_total != nullptr && digit_total != nullptr, "pxd_cluster_stats: cluster_total / digit_total is NULL");
-    CHECK_ARG(tables != nullptr && overflow != nullptr && (((uintptr_t)tables | (uintptr_t)overflow) & 7u) == 0,
-              "pxd_cluster_stats: tables / overflow is NULL or not 8-byte aligned");
+    const char* who = "pxd_cluster_stats";
+    if (int rc = pxd_check_geometry(who, N, H, W, true)) return rc;
+    if (int rc = pxd_check_whole_events(who, N, n_sensors)) return rc;
+    if (int rc = pxd_check_capacity(who, "capacity", capacity)) return rc;
+    if (int rc = pxd_check_arrays(who, "a cluster table", "capacity", capacity, {first, size, ccharge, seed, size_u, size_v})) return rc;
+    if (int rc = pxd_check_totals(who, "cluster_total / digit_total", {cluster_total, digit_total})) return rc;
+    if (int rc = pxd_check_needed(who, "tables / overflow", 8, {tables, overflow})) return rc;
     const int cap = pxd_cap(capacity);
-    ProfScope prof("pxd_cluster_stats", 0.0, 0.0, st);
+    ProfScope prof(who, 0.0, 0.0, st);
     hipLaunchKernelGGL(pxd_cluster_stats_kernel, dim3(cl_blocks(cap)), dim3(PXD_THREADS), 0, st, first, size, ccharge, (const uint8_t*)seed, size_u,
                        size_v, cluster_total, digit_total, cap, H * W, n_sensors, tables, overflow);
     CHECK_LAUNCH("pxd_cluster_stats");

@@ -16,7 +16,7 @@
 // stream); a rank is counted by one thread.  Two calls on the same input write the same bytes.
 //
 // Kernels.
-//   counts   the launch partition of the digit-list kernels (cl_blocks / cl_chunk): one lane per digit below min(total, capacity).  Digits
+//   counts   the launch partition of the digit-list kernels (cl_blocks / cl_chunk): one lane per digit below pxd_total.  Digits
 //            ascend in flat index, so the 64 digits of a wave's step fall into few runs of equal (e, k): pxd_run / pxd_run_sum and one
 //            atomicAdd per run.  x is zeroed by a launch of its own in front.
 //   gram     thread (i, j): the lanes of a wave are 64 consecutive columns j (x[e, j] is one 256-byte access) and the wave holds GR_ROWS rows
@@ -35,9 +35,6 @@
 #include "common.h"
 #include "pxd_common.h"
 
-typedef long long i64;
-typedef unsigned long long u64;
-
 #define CORR_MAX_COLUMNS 1024
 #define CORR_MAX_EVENTS 65535
 #define GR_ROWS 4               // rows i of a wave of the Gram kernel
@@ -46,22 +43,19 @@ typedef unsigned long long u64;
 #define RK_DEPTH 4              // rows e' of x it loads before it uses the first
 
 __global__ __launch_bounds__(PXD_THREADS) void pxd_corr_zero_kernel(int* __restrict__ x, long n) {
-    for (long t = (long)blockIdx.x * PXD_THREADS + threadIdx.x; t < n; t += (long)gridDim.x * PXD_THREADS) x[t] = 0;
+    for (long t = pxd_grid_thread(); t < n; t += pxd_grid_threads()) x[t] = 0;
 }
 
 __global__ __launch_bounds__(PXD_THREADS) void pxd_region_counts_kernel(const int* __restrict__ index, const int* __restrict__ dtotal, int cap,
                                                                         int chunk, long NHW, int HW, int H, int W, int S, int RU, int RV,
                                                                         int* __restrict__ x, u64* __restrict__ overflow) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
     if (blockIdx.x == 0 && threadIdx.x == 0 && dtotal[0] > cap) atomicAdd(overflow, 1ull);
-    const long M = max(min(dtotal[0], cap), 0);
-    const int R = S * RU * RV;
-    const long k0 = (long)g * chunk;
-    const long k1 = k0 + chunk < M ? k0 + chunk : M;
-    for (long kb = k0; kb < k1; kb += 64) {         // wave-uniform bounds
+    const PxdWaveRange w(pxd_total(dtotal, cap), chunk);
+    const int R = S * RU * RV, lane = w.lane;
+    for (long kb = w.k0; kb < w.k1; kb += 64) {
         const long kk = kb + lane;
         int lab = -1;                               // no digit, or a flat index outside the batch
-        if (kk < k1) {
+        if (kk < w.k1) {
             const int idx = index[kk];
             if (idx >= 0 && (long)idx < NHW) {
                 int r, c;
@@ -154,8 +148,7 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_ranks_kernel(const int* __res
 static int corr_check_table(const char* who, const void* x, int E, int R) {
     CHECK_ARG(E >= 1 && E <= CORR_MAX_EVENTS, "%s: E = %d outside 1 .. %d", who, E, CORR_MAX_EVENTS);
     CHECK_ARG(R >= 1 && R <= CORR_MAX_COLUMNS, "%s: R = %d outside 1 .. %d", who, R, CORR_MAX_COLUMNS);
-    CHECK_ARG(x != nullptr && ((uintptr_t)x & 3u) == 0, "%s: x is NULL or not 4-byte aligned", who);
-    return 0;
+    return pxd_check_needed(who, "x", 4, {x});
 }
 
 extern "C" int ieagan_pxd_region_counts(const int* index, const int* digit_total, int N, int H, int W, int n_sensors, int RU, int RV,
@@ -163,15 +156,15 @@ extern "C" int ieagan_pxd_region_counts(const int* index, const int* digit_total
     const char* who = "pxd_region_counts";
     hipStream_t st = (hipStream_t)stream;
     if (int rc = pxd_check_geometry(who, N, H, W, true)) return rc;
-    CHECK_ARG(n_sensors > 0 && N % n_sensors == 0, "%s: N = %d is not a multiple of n_sensors = %d", who, N, n_sensors);
+    if (int rc = pxd_check_whole_events(who, N, n_sensors)) return rc;
     CHECK_ARG(RU >= 1 && RU <= H && RV >= 1 && RV <= W, "%s: regions %d x %d outside 1 .. %d x 1 .. %d", who, RU, RV, H, W);
     CHECK_ARG((long)n_sensors * RU * RV <= CORR_MAX_COLUMNS, "%s: R = %d * %d * %d columns exceed %d", who, n_sensors, RU, RV, CORR_MAX_COLUMNS);
-    CHECK_ARG(capacity >= 0, "%s: capacity = %ld is negative", who, capacity);
-    CHECK_ARG(digit_total != nullptr && ((uintptr_t)digit_total & 3u) == 0, "%s: digit_total is NULL or misaligned", who);
-    CHECK_ARG((capacity == 0 || index != nullptr) && ((uintptr_t)index & 3u) == 0, "%s: index is NULL with capacity %ld or not 4-byte aligned", who,
-              capacity);
-    CHECK_ARG(x != nullptr && ((uintptr_t)x & 3u) == 0, "%s: x is NULL or not 4-byte aligned", who);
-    CHECK_ARG(overflow != nullptr && ((uintptr_t)overflow & 7u) == 0, "%s: overflow is NULL or not 8-byte aligned", who);
+    if (int rc = pxd_check_capacity(who, "capacity", capacity)) return rc;
+    if (int rc = pxd_check_totals(who, "digit_total", {digit_total})) return rc;
+    if (int rc = pxd_check_arrays(who, "index", "capacity", capacity, {index})) return rc;
+    if (int rc = pxd_check_aligned(who, "index", 4, {index})) return rc;
+    if (int rc = pxd_check_needed(who, "x", 4, {x})) return rc;
+    if (int rc = pxd_check_needed(who, "overflow", 8, {overflow})) return rc;
     const int cap = pxd_cap(capacity);
     const int B = cl_blocks(cap), chunk = cl_chunk(cap, B);
     const long cells = (long)(N / n_sensors) * n_sensors * RU * RV;
@@ -189,8 +182,7 @@ extern "C" int ieagan_pxd_gram(const int* x, int E, int R, long long* gram, long
     const char* who = "pxd_gram";
     hipStream_t st = (hipStream_t)stream;
     if (int rc = corr_check_table(who, x, E, R)) return rc;
-    CHECK_ARG(gram != nullptr && sum != nullptr && (((uintptr_t)gram | (uintptr_t)sum) & 7u) == 0, "%s: gram / sum is NULL or not 8-byte aligned",
-              who);
+    if (int rc = pxd_check_needed(who, "gram / sum", 8, {gram, sum})) return rc;
     const int rows = GR_ROWS * PXD_WAVES;
     ProfScope prof(who, 2.0 * E * R * R, 4.0 * E * R + 16.0 * R * R, st);
     hipLaunchKernelGGL(pxd_gram_kernel, dim3((R + 63) / 64, (R + rows - 1) / rows), dim3(PXD_THREADS), 0, st, x, E, R, (i64*)gram, (i64*)sum);
@@ -202,7 +194,7 @@ extern "C" int ieagan_pxd_ranks(const int* x, int E, int R, int* rank2, void* st
     const char* who = "pxd_ranks";
     hipStream_t st = (hipStream_t)stream;
     if (int rc = corr_check_table(who, x, E, R)) return rc;
-    CHECK_ARG(rank2 != nullptr && ((uintptr_t)rank2 & 3u) == 0, "%s: rank2 is NULL or not 4-byte aligned", who);
+    if (int rc = pxd_check_needed(who, "rank2", 4, {rank2})) return rc;
     CHECK_ARG(rank2 != x, "%s: rank2 must not be x", who);
     const int rows = RK_OWN * PXD_WAVES;
     ProfScope prof(who, 2.0 * E * E * R, 8.0 * E * R, st);

@@ -25,17 +25,11 @@
 #include "common.h"
 #include "pxd_common.h"
 
-typedef long long i64;
-typedef unsigned long long u64;
-
 __global__ __launch_bounds__(PXD_THREADS) void pxd_hits_init_kernel(const int* __restrict__ ctotal, int cap, int chunk, i64* __restrict__ pu,
                                                                     i64* __restrict__ pv, int* __restrict__ v_start, int* __restrict__ qh_u,
                                                                     int* __restrict__ qt_u, int* __restrict__ qh_v, int* __restrict__ qt_v) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
-    const long T = max(min(ctotal[0], cap), 0);
-    const long j0 = (long)g * chunk;
-    const long j1 = j0 + chunk < T ? j0 + chunk : T;
-    for (long jj = j0 + lane; jj < j1; jj += 64) {
+    const PxdWaveRange w(pxd_total(ctotal, cap), chunk);
+    for (long jj = w.k0 + w.lane; jj < w.k1; jj += 64) {
         const int j = (int)jj;
         pu[j] = 0ll;
         pv[j] = 0ll;
@@ -47,8 +41,8 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_hits_init_kernel(const int* _
 // The digit k of lane `lane` in the step at kb, or lab = -1: no digit, a label that is no row of the table, or a position outside the batch.
 __device__ __forceinline__ int hits_digit(const int* __restrict__ index, const int* __restrict__ label, long kk, long k1, int T, long NHW,
                                           int HW, int W, int& r, int& c, int& idx) {
-    int lab = kk < k1 ? label[kk] : -1;
-    if ((unsigned)lab >= (unsigned)T) return -1;
+    const int lab = pxd_digit_label(label, kk, k1, T);
+    if (lab < 0) return -1;
     idx = index[kk];
     if (idx < 0 || (long)idx >= NHW) return -1;
     pxd_row_col(idx, HW, W, r, c);
@@ -60,15 +54,12 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_hits_moments_kernel(
     const int* __restrict__ first, const int* __restrict__ size_u, const int* __restrict__ ctotal, const int* __restrict__ u_x2,
     const int* __restrict__ v_x2, const int* __restrict__ kind, int cap, int chunk, int N, int H, int W, int n_sensors, int K,
     i64* __restrict__ pu, i64* __restrict__ pv, int* __restrict__ v_start, int* __restrict__ qh_u, int* __restrict__ qt_u) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
-    const long M = min(dtotal[0], cap);
-    const int T = min(ctotal[0], cap);
+    const PxdWaveRange w(pxd_total(dtotal, cap), chunk);
+    const int T = pxd_total(ctotal, cap), lane = w.lane;
     const int HW = H * W;
-    const long k0 = (long)g * chunk;
-    const long k1 = k0 + chunk < M ? k0 + chunk : M;
-    for (long kb = k0; kb < k1; kb += 64) {         // wave-uniform bounds
+    for (long kb = w.k0; kb < w.k1; kb += 64) {
         int r = 0, c = INT_MAX, idx = 0;
-        const int lab = hits_digit(index, label, kb + lane, k1, T, (long)N * HW, HW, W, r, c, idx);
+        const int lab = hits_digit(index, label, kb + lane, w.k1, T, (long)N * HW, HW, W, r, c, idx);
         i64 mu = 0ll, mv = 0ll;
         int head = 0, tail = 0;
         if (lab >= 0) {
@@ -103,15 +94,12 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_hits_edges_kernel(const int* 
                                                                      const int* __restrict__ size_v, const int* __restrict__ ctotal,
                                                                      const int* __restrict__ v_start, int cap, int chunk, int N, int H, int W,
                                                                      int* __restrict__ qh_v, int* __restrict__ qt_v) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
-    const long M = min(dtotal[0], cap);
-    const int T = min(ctotal[0], cap);
+    const PxdWaveRange w(pxd_total(dtotal, cap), chunk);
+    const int T = pxd_total(ctotal, cap), lane = w.lane;
     const int HW = H * W;
-    const long k0 = (long)g * chunk;
-    const long k1 = k0 + chunk < M ? k0 + chunk : M;
-    for (long kb = k0; kb < k1; kb += 64) {         // wave-uniform bounds
+    for (long kb = w.k0; kb < w.k1; kb += 64) {
         int r = 0, c = 0, idx = 0;
-        const int lab = hits_digit(index, label, kb + lane, k1, T, (long)N * HW, HW, W, r, c, idx);
+        const int lab = hits_digit(index, label, kb + lane, w.k1, T, (long)N * HW, HW, W, r, c, idx);
         int head = 0, tail = 0;
         if (lab >= 0) {
             const int q = (int)charge[kb + lane], lo = v_start[lab];
@@ -162,10 +150,10 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_hits_kernel(
     int W, int n_sensors, int K, int head_tail, const i64* __restrict__ pu, const i64* __restrict__ pv, const int* __restrict__ v_start,
     const int* __restrict__ qh_u, const int* __restrict__ qt_u, const int* __restrict__ qh_v, const int* __restrict__ qt_v, float* __restrict__ u,
     float* __restrict__ v, uint8_t* __restrict__ flags) {
-    const int T = max(min(ctotal[0], cap), 0);
-    const int A = min(atotal[0], T);
+    const int T = pxd_total(ctotal, cap);
+    const int A = pxd_total(atotal, T);
     const int HW = H * W;
-    for (int a = blockIdx.x * PXD_THREADS + threadIdx.x; a < A; a += gridDim.x * PXD_THREADS) {
+    for (int a = pxd_grid_thread(); a < A; a += pxd_grid_threads()) {
         const int j = cluster[a];
         float pos_u = 0.0f, pos_v = 0.0f;
         bool ht_u = false, ht_v = false, cl_u = false, cl_v = false;
@@ -197,34 +185,28 @@ extern "C" int ieagan_pxd_hits(const int* index, const unsigned char* charge, co
                                unsigned char* flags, int* scratch, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     (void)scratch;
-    if (int rc = pxd_check_geometry("pxd_hits", N, H, W, true)) return rc;
-    CHECK_ARG((double)H * W * 255.0 < 2147483648.0, "pxd_hits: H * W * 255 = %d * %d * 255 does not fit the int32 cluster charge", H, W);
-    CHECK_ARG(n_sensors > 0 && N % n_sensors == 0, "pxd_hits: N = %d is not a multiple of n_sensors = %d", N, n_sensors);
-    CHECK_ARG(K >= 1, "pxd_hits: K = %d sensor types", K);
-    CHECK_ARG(capacity >= 0, "pxd_hits: capacity = %ld is negative", capacity);
-    CHECK_ARG(head_tail == 0 || head_tail >= 3, "pxd_hits: head_tail = %d is neither 0 (never) nor >= 3", head_tail);
-    CHECK_ARG(digit_total != nullptr && cluster_total != nullptr && accepted_total != nullptr &&
-              (((uintptr_t)digit_total | (uintptr_t)cluster_total | (uintptr_t)accepted_total) & 3u) == 0,
-              "pxd_hits: digit_total / cluster_total / accepted_total is NULL or misaligned");
+    const char* who = "pxd_hits";
+    if (int rc = pxd_check_geometry(who, N, H, W, true)) return rc;
+    if (int rc = pxd_check_cluster_charge(who, H, W)) return rc;
+    if (int rc = pxd_check_whole_events(who, N, n_sensors)) return rc;
+    CHECK_ARG(K >= 1, "%s: K = %d sensor types", who, K);
+    if (int rc = pxd_check_capacity(who, "capacity", capacity)) return rc;
+    CHECK_ARG(head_tail == 0 || head_tail >= 3, "%s: head_tail = %d is neither 0 (never) nor >= 3", who, head_tail);
+    if (int rc = pxd_check_totals(who, "digit_total / cluster_total / accepted_total", {digit_total, cluster_total, accepted_total})) return rc;
     // the content of the tables (pitch 1 .. 4095, length < 2^20, kind < K) is checked on the host by pxd.PXDGeometry: the launcher cannot see
     // device memory.  The kernels never index a table with a type outside 0 .. K-1.
-    CHECK_ARG(u_x2 != nullptr && u_pitch != nullptr && v_x2 != nullptr && v_pitch != nullptr && kind != nullptr &&
-              (((uintptr_t)u_x2 | (uintptr_t)u_pitch | (uintptr_t)v_x2 | (uintptr_t)v_pitch | (uintptr_t)kind) & 3u) == 0,
-              "pxd_hits: a geometry table is NULL or misaligned");
-    CHECK_ARG(capacity == 0 || (index != nullptr && charge != nullptr && label != nullptr),
-              "pxd_hits: index / charge / label is NULL with capacity %ld", capacity);
-    CHECK_ARG(capacity == 0 || (first != nullptr && ccharge != nullptr && size_u != nullptr && size_v != nullptr && cluster != nullptr),
-              "pxd_hits: a cluster table or the accepted list is NULL with capacity %ld", capacity);
-    CHECK_ARG(capacity == 0 || (pu != nullptr && pv != nullptr && v_start != nullptr && qh_u != nullptr && qt_u != nullptr && qh_v != nullptr &&
-                                qt_v != nullptr && u != nullptr && v != nullptr && flags != nullptr),
-              "pxd_hits: an output array is NULL with capacity %ld", capacity);
-    CHECK_ARG((((uintptr_t)index | (uintptr_t)label | (uintptr_t)first | (uintptr_t)ccharge | (uintptr_t)size_u | (uintptr_t)size_v |
-                (uintptr_t)cluster | (uintptr_t)v_start | (uintptr_t)qh_u | (uintptr_t)qt_u | (uintptr_t)qh_v | (uintptr_t)qt_v | (uintptr_t)u |
-                (uintptr_t)v) & 3u) == 0, "pxd_hits: an int32 / fp32 array is not 4-byte aligned");
-    CHECK_ARG((((uintptr_t)pu | (uintptr_t)pv) & 7u) == 0, "pxd_hits: pu / pv is not 8-byte aligned");
+    if (int rc = pxd_check_needed(who, "a geometry table", 4, {u_x2, u_pitch, v_x2, v_pitch, kind})) return rc;
+    if (int rc = pxd_check_arrays(who, "index / charge / label", "capacity", capacity, {index, charge, label})) return rc;
+    if (int rc = pxd_check_arrays(who, "a cluster table or the accepted list", "capacity", capacity, {first, ccharge, size_u, size_v, cluster}))
+        return rc;
+    if (int rc = pxd_check_arrays(who, "an output array", "capacity", capacity, {pu, pv, v_start, qh_u, qt_u, qh_v, qt_v, u, v, flags})) return rc;
+    if (int rc = pxd_check_aligned(who, "an int32 / fp32 array", 4,
+                                   {index, label, first, ccharge, size_u, size_v, cluster, v_start, qh_u, qt_u, qh_v, qt_v, u, v}))
+        return rc;
+    if (int rc = pxd_check_aligned(who, "pu / pv", 8, {pu, pv})) return rc;
     const int cap = pxd_cap(capacity);
     const int B = cl_blocks(cap), chunk = cl_chunk(cap, B);
-    ProfScope prof("pxd_hits", 0.0, 0.0, st);
+    ProfScope prof(who, 0.0, 0.0, st);
     hipLaunchKernelGGL(pxd_hits_init_kernel, dim3(B), dim3(PXD_THREADS), 0, st, cluster_total, cap, chunk, (i64*)pu, (i64*)pv, v_start, qh_u, qt_u,
                        qh_v, qt_v);
     CHECK_LAUNCH("pxd_hits init");

@@ -38,9 +38,6 @@
 #include "common.h"
 #include "pxd_common.h"
 
-typedef long long i64;
-typedef unsigned long long u64;
-
 #define MT_MAX_BLOCKS 4096
 #define MT_MATCHED 1
 #define MT_CHANGED 2
@@ -51,22 +48,15 @@ typedef unsigned long long u64;
 
 // One wave per 64 entries of the capacity up to MT_MAX_BLOCKS workgroups (the reasoning of ov_blocks in pxd_overlay.hip: a production event
 // is one step per wave, the dependent loads of all searches run side by side).
-static inline int mt_blocks(long cap) {
-    long b = (cap + PXD_THREADS - 1) / PXD_THREADS;
-    if (b > MT_MAX_BLOCKS) b = MT_MAX_BLOCKS;
-    return (int)(b < 1 ? 1 : b);
-}
-
-// A total read on the device, clipped to [0, cap].
-__device__ __forceinline__ int mt_total(const int* __restrict__ total, int cap) { return max(min(total[0], cap), 0); }
+static inline int mt_blocks(long cap) { return pxd_blocks(cap, PXD_THREADS, MT_MAX_BLOCKS); }
 
 __global__ __launch_bounds__(PXD_THREADS) void pxd_match_init_kernel(const int* __restrict__ s_ctotal, int s_cap, const int* __restrict__ m_ctotal,
                                                                      int m_cap, int* __restrict__ found, int* __restrict__ lo,
                                                                      int* __restrict__ hi, int* __restrict__ signal_size,
                                                                      int* __restrict__ signal_charge, int* __restrict__ n_signal,
                                                                      int* __restrict__ inv) {
-    const int Ts = mt_total(s_ctotal, s_cap), Tm = mt_total(m_ctotal, m_cap);
-    const long t0 = (long)blockIdx.x * PXD_THREADS + threadIdx.x, step = (long)gridDim.x * PXD_THREADS;
+    const int Ts = pxd_total(s_ctotal, s_cap), Tm = pxd_total(m_ctotal, m_cap);
+    const long t0 = pxd_grid_thread(), step = pxd_grid_threads();
     for (long j = t0; j < Ts; j += step) {
         found[j] = 0;
         lo[j] = INT_MAX;
@@ -83,16 +73,12 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_match_digits_kernel(
     const int* __restrict__ s_ctotal, int s_cap, const int* __restrict__ m_index, const int* __restrict__ m_label,
     const int* __restrict__ m_dtotal, const int* __restrict__ m_ctotal, int m_cap, int chunk, int* __restrict__ found, int* __restrict__ lo,
     int* __restrict__ hi, int* __restrict__ signal_size, int* __restrict__ signal_charge) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
-    const long Ms = mt_total(s_dtotal, s_cap);
-    const int Mm = mt_total(m_dtotal, m_cap);
-    const int Ts = mt_total(s_ctotal, s_cap), Tm = mt_total(m_ctotal, m_cap);
-    const long k0 = (long)g * chunk;
-    const long k1 = k0 + chunk < Ms ? k0 + chunk : Ms;
-    for (long kb = k0; kb < k1; kb += 64) {         // wave-uniform bounds
+    const PxdWaveRange w(pxd_total(s_dtotal, s_cap), chunk);
+    const int lane = w.lane, Mm = pxd_total(m_dtotal, m_cap);
+    const int Ts = pxd_total(s_ctotal, s_cap), Tm = pxd_total(m_ctotal, m_cap);
+    for (long kb = w.k0; kb < w.k1; kb += 64) {
         const long kk = kb + lane;
-        int lab = kk < k1 ? s_label[kk] : -1;
-        if ((unsigned)lab >= (unsigned)Ts) lab = -1;            // no digit, or a label that is no row of the signal table
+        const int lab = pxd_digit_label(s_label, kk, w.k1, Ts);
         int L = -1, q = 0;
         if (lab >= 0) {
             const int idx = s_index[kk];
@@ -130,9 +116,9 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_match_clusters_kernel(const i
                                                                          const int* __restrict__ found, int* __restrict__ lo,
                                                                          int* __restrict__ hi, int* __restrict__ n_signal,
                                                                          int* __restrict__ inv) {
-    const int Ts = mt_total(s_ctotal, s_cap), Tm = mt_total(m_ctotal, m_cap);
-    const int Am = min(max(m_atotal[0], 0), Tm);
-    const long t0 = (long)blockIdx.x * PXD_THREADS + threadIdx.x, step = (long)gridDim.x * PXD_THREADS;
+    const int Ts = pxd_total(s_ctotal, s_cap), Tm = pxd_total(m_ctotal, m_cap);
+    const int Am = pxd_total(m_atotal, Tm);
+    const long t0 = pxd_grid_thread(), step = pxd_grid_threads();
     for (long j = t0; j < Ts; j += step) {
         const int l = lo[j];
         if (found[j] <= 0 || (unsigned)l >= (unsigned)Tm) lo[j] = hi[j] = -1;
@@ -151,9 +137,9 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_match_hits_kernel(
     const float* __restrict__ m_u, const float* __restrict__ m_v, const int* __restrict__ found, const int* __restrict__ lo,
     const int* __restrict__ hi, const int* __restrict__ n_signal, const int* __restrict__ inv, int* __restrict__ mixed_hit,
     uint8_t* __restrict__ flags, float* __restrict__ du, float* __restrict__ dv) {
-    const int Ts = mt_total(s_ctotal, s_cap), Tm = mt_total(m_ctotal, m_cap);
-    const int As = min(max(s_atotal[0], 0), Ts), Am = min(max(m_atotal[0], 0), Tm);
-    const long t0 = (long)blockIdx.x * PXD_THREADS + threadIdx.x, step = (long)gridDim.x * PXD_THREADS;
+    const int Ts = pxd_total(s_ctotal, s_cap), Tm = pxd_total(m_ctotal, m_cap);
+    const int As = pxd_total(s_atotal, Ts), Am = pxd_total(m_atotal, Tm);
+    const long t0 = pxd_grid_thread(), step = pxd_grid_threads();
     for (long h = t0; h < As; h += step) {
         const int j = s_cluster[h];
         int mh = -1, fl = 0;
@@ -191,10 +177,10 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_match_stats_kernel(
     int m_cap, const float* __restrict__ m_u, const float* __restrict__ m_v, const int* __restrict__ lo, const int* __restrict__ signal_charge,
     const int* __restrict__ mixed_hit, const uint8_t* __restrict__ flags, int N, int H, int W, int n_sensors, double w, u64* __restrict__ table,
     u64* __restrict__ overflow) {
-    const long t0 = (long)blockIdx.x * PXD_THREADS + threadIdx.x, step = (long)gridDim.x * PXD_THREADS;
+    const long t0 = pxd_grid_thread(), step = pxd_grid_threads();
     if (t0 == 0 && (s_dtotal[0] > s_cap || m_dtotal[0] > m_cap)) atomicAdd(overflow, 1ull);
-    const int Ts = mt_total(s_ctotal, s_cap), Tm = mt_total(m_ctotal, m_cap);
-    const int As = min(max(s_atotal[0], 0), Ts), Am = min(max(m_atotal[0], 0), Tm);
+    const int Ts = pxd_total(s_ctotal, s_cap), Tm = pxd_total(m_ctotal, m_cap);
+    const int As = pxd_total(s_atotal, Ts), Am = pxd_total(m_atotal, Tm);
     const int HW = H * W;
     for (long h = t0; h < As; h += step) {
         const int j = s_cluster[h];
@@ -228,25 +214,17 @@ extern "C" long ieagan_pxd_match_scratch(int N, int H, int W, long capacity) {
     return (long)pxd_cap(capacity);             // the inverse map: one word per mixed cluster
 }
 
-static int mt_check_side(const char* who, const char* side, long capacity, const void* const* i32, int n_i32, const void* const* totals,
-                         int n_totals) {
-    CHECK_ARG(capacity >= 0, "%s: %s_capacity = %ld is negative", who, side, capacity);
-    uintptr_t any = 0;
-    bool null_total = false, null_array = false;
-    for (int k = 0; k < n_totals; ++k) {
-        any |= (uintptr_t)totals[k];
-        null_total |= totals[k] == nullptr;
-    }
-    CHECK_ARG(!null_total && (any & 3u) == 0, "%s: a total of the %s side is NULL or misaligned", who, side);
-    any = 0;
-    for (int k = 0; k < n_i32; ++k) {
-        any |= (uintptr_t)i32[k];
-        null_array |= i32[k] == nullptr;
-    }
-    CHECK_ARG(capacity == 0 || !null_array, "%s: an array of the %s side is NULL with capacity %ld", who, side, capacity);
-    CHECK_ARG((any & 3u) == 0, "%s: an int32 / fp32 array of the %s side is not 4-byte aligned", who, side);
-    return 0;
+// One side: `names` are its capacity, totals, arrays and 4-byte arrays in the error texts.
+static int mt_check_side(const char* who, const char* const names[4], long capacity, PxdPtrs totals, PxdPtrs i32) {
+    if (int rc = pxd_check_capacity(who, names[0], capacity)) return rc;
+    if (int rc = pxd_check_totals(who, names[1], totals)) return rc;
+    if (int rc = pxd_check_arrays(who, names[2], "capacity", capacity, i32)) return rc;
+    return pxd_check_aligned(who, names[3], 4, i32);
 }
+static const char* const MT_SIGNAL[4] = {"signal_capacity", "a total of the signal side", "an array of the signal side",
+                                         "an int32 / fp32 array of the signal side"};
+static const char* const MT_MIXED[4] = {"mixed_capacity", "a total of the mixed side", "an array of the mixed side",
+                                        "an int32 / fp32 array of the mixed side"};
 
 extern "C" int ieagan_pxd_match(const int* s_index, const unsigned char* s_charge, const int* s_label, const int* s_digit_total,
                                 const int* s_size, const int* s_ccharge, const int* s_cluster_total, const int* s_cluster,
@@ -258,18 +236,14 @@ extern "C" int ieagan_pxd_match(const int* s_index, const unsigned char* s_charg
     const char* who = "pxd_match";
     hipStream_t st = (hipStream_t)stream;
     if (int rc = pxd_check_geometry(who, N, H, W, true)) return rc;
-    {
-        const void* arrays[] = {s_index, s_label, s_size, s_ccharge, s_cluster, s_u, s_v, found, lo, hi, mixed_hit, du, dv};
-        const void* totals[] = {s_digit_total, s_cluster_total, s_accepted_total};
-        if (int rc = mt_check_side(who, "signal", s_capacity, arrays, 13, totals, 3)) return rc;
-        CHECK_ARG(s_capacity == 0 || (s_charge != nullptr && flags != nullptr), "%s: s_charge / flags is NULL with capacity %ld", who, s_capacity);
-    }
-    {
-        const void* arrays[] = {m_index, m_label, m_size, m_ccharge, m_cluster, m_u, m_v, signal_size, signal_charge, n_signal};
-        const void* totals[] = {m_digit_total, m_cluster_total, m_accepted_total};
-        if (int rc = mt_check_side(who, "mixed", m_capacity, arrays, 10, totals, 3)) return rc;
-    }
-    CHECK_ARG(((uintptr_t)scratch & 3u) == 0 && (m_capacity == 0 || scratch != nullptr),
+    if (int rc = mt_check_side(who, MT_SIGNAL, s_capacity, {s_digit_total, s_cluster_total, s_accepted_total},
+                               {s_index, s_label, s_size, s_ccharge, s_cluster, s_u, s_v, found, lo, hi, mixed_hit, du, dv}))
+        return rc;
+    if (int rc = pxd_check_arrays(who, "s_charge / flags", "capacity", s_capacity, {s_charge, flags})) return rc;
+    if (int rc = mt_check_side(who, MT_MIXED, m_capacity, {m_digit_total, m_cluster_total, m_accepted_total},
+                               {m_index, m_label, m_size, m_ccharge, m_cluster, m_u, m_v, signal_size, signal_charge, n_signal}))
+        return rc;
+    CHECK_ARG(pxd_all_aligned({scratch}, 4) && (m_capacity == 0 || scratch != nullptr),
               "%s: scratch (ieagan_pxd_match_scratch int32 words) is NULL or misaligned", who);
     const int s_cap = pxd_cap(s_capacity), m_cap = pxd_cap(m_capacity);
     const int B = mt_blocks(s_cap > m_cap ? s_cap : m_cap), chunk = cl_chunk(s_cap, B);
@@ -302,21 +276,16 @@ extern "C" int ieagan_pxd_match_stats(const int* s_cluster, const int* s_accepte
     const char* who = "pxd_match_stats";
     hipStream_t st = (hipStream_t)stream;
     if (int rc = pxd_check_geometry(who, N, H, W, true)) return rc;
-    CHECK_ARG(n_sensors > 0 && N % n_sensors == 0, "%s: N = %d is not a multiple of n_sensors = %d", who, N, n_sensors);
+    if (int rc = pxd_check_whole_events(who, N, n_sensors)) return rc;
     CHECK_ARG(residual_bin >= 1, "%s: residual_bin = %d is not >= 1", who, residual_bin);
-    {
-        const void* arrays[] = {s_cluster, s_first, s_u, s_v, lo, mixed_hit};
-        const void* totals[] = {s_digit_total, s_cluster_total, s_accepted_total};
-        if (int rc = mt_check_side(who, "signal", s_capacity, arrays, 6, totals, 3)) return rc;
-        CHECK_ARG(s_capacity == 0 || flags != nullptr, "%s: flags is NULL with capacity %ld", who, s_capacity);
-    }
-    {
-        const void* arrays[] = {m_ccharge, m_u, m_v, signal_charge};
-        const void* totals[] = {m_digit_total, m_cluster_total, m_accepted_total};
-        if (int rc = mt_check_side(who, "mixed", m_capacity, arrays, 4, totals, 3)) return rc;
-    }
-    CHECK_ARG(table != nullptr && overflow != nullptr && (((uintptr_t)table | (uintptr_t)overflow) & 7u) == 0,
-              "%s: table / overflow is NULL or not 8-byte aligned", who);
+    if (int rc = mt_check_side(who, MT_SIGNAL, s_capacity, {s_digit_total, s_cluster_total, s_accepted_total},
+                               {s_cluster, s_first, s_u, s_v, lo, mixed_hit}))
+        return rc;
+    if (int rc = pxd_check_arrays(who, "flags", "capacity", s_capacity, {flags})) return rc;
+    if (int rc = mt_check_side(who, MT_MIXED, m_capacity, {m_digit_total, m_cluster_total, m_accepted_total},
+                               {m_ccharge, m_u, m_v, signal_charge}))
+        return rc;
+    if (int rc = pxd_check_needed(who, "table / overflow", 8, {table, overflow})) return rc;
     const int s_cap = pxd_cap(s_capacity), m_cap = pxd_cap(m_capacity);
     ProfScope prof(who, 0.0, 0.0, st);
     hipLaunchKernelGGL(pxd_match_stats_kernel, dim3(cl_blocks(s_cap)), dim3(PXD_THREADS), 0, st, s_cluster, s_accepted_total, s_first,

@@ -36,11 +36,7 @@
 #include "pxd_common.h"
 
 #define OV_MAX_BLOCKS 4096          // 4 tiles of pxd_scan_slots at the most
-static inline int ov_blocks(long cap) {
-    long b = (cap + PXD_THREADS - 1) / PXD_THREADS;
-    if (b > OV_MAX_BLOCKS) b = OV_MAX_BLOCKS;
-    return (int)(b < 1 ? 1 : b);
-}
+static inline int ov_blocks(long cap) { return pxd_blocks(cap, PXD_THREADS, OV_MAX_BLOCKS); }
 
 struct OvStore {
     const int* pos;
@@ -80,12 +76,7 @@ __global__ __launch_bounds__(PXD_SCAN_THREADS) void pxd_overlay_sum_kernel(OvSto
         ov_range(B, e, d0, nb);
         mine += (long)na + nb;
     }
-    long incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long y = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += y;
-    }
+    const long incl = pxd_wave_scan(mine, lane);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
     long run = incl - mine;
@@ -170,23 +161,19 @@ __device__ __forceinline__ long ov_chunk(int total, int waves) {
 
 __global__ __launch_bounds__(PXD_THREADS) void pxd_overlay_count_kernel(OvStore A, OvStore B, int E, const int* __restrict__ U,
                                                                         int* __restrict__ slots) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
-    const long M = U[E];
-    const long chunk = ov_chunk((int)M, gridDim.x * PXD_WAVES);
-    const long k0 = (long)g * chunk;
-    const long k1 = k0 + chunk < M ? k0 + chunk : M;
+    const PxdWaveRange w(U[E], ov_chunk(U[E], gridDim.x * PXD_WAVES));
     int kept = 0, e = 0;
-    for (long kb = k0; kb < k1; kb += 64) {             // wave-uniform bounds
-        const long t = kb + lane;
+    for (long kb = w.k0; kb < w.k1; kb += 64) {
+        const long t = kb + w.lane;
         bool keep = false;
-        if (t < k1) {
+        if (t < w.k1) {
             const OvItem it = ov_item<false>(A, B, E, U, (int)t, e);
             e = it.e;
             keep = it.kept;
         }
         kept += __popcll(__ballot(keep));
     }
-    if (lane == 0) slots[g] = kept;                     // every slot of the launch, also of a wave without a range
+    if (w.lane == 0) slots[w.g] = kept;                 // every slot of the launch, also of a wave without a range
 }
 
 // The prefix sum of pxd_common.h over the wave slots of the count launch; the total goes to out_offsets[E] and to the trailing empty pairs
@@ -202,22 +189,19 @@ __global__ __launch_bounds__(PXD_SCAN_THREADS) void pxd_overlay_scan_kernel(int*
 __global__ __launch_bounds__(PXD_THREADS) void pxd_overlay_write_kernel(OvStore A, OvStore B, int E, const int* __restrict__ U,
                                                                         const int* __restrict__ slots, int cap, int* __restrict__ out_pos,
                                                                         uint8_t* __restrict__ out_charge, long* __restrict__ out_offsets) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
-    const long M = U[E];
-    const long chunk = ov_chunk((int)M, gridDim.x * PXD_WAVES);
-    const long k0 = (long)g * chunk;
-    const long k1 = k0 + chunk < M ? k0 + chunk : M;
-    int run = slots[g], e = 0;
-    for (long kb = k0; kb < k1; kb += 64) {             // wave-uniform bounds
+    const PxdWaveRange w(U[E], ov_chunk(U[E], gridDim.x * PXD_WAVES));
+    const int lane = w.lane;
+    int run = slots[w.g], e = 0;
+    for (long kb = w.k0; kb < w.k1; kb += 64) {
         const long t = kb + lane;
         OvItem it;
         it.e = e;
         it.pos = it.q = 0;
         it.kept = it.first = false;
-        if (t < k1) it = ov_item<true>(A, B, E, U, (int)t, e);
+        if (t < w.k1) it = ov_item<true>(A, B, E, U, (int)t, e);
         e = it.e;
         const unsigned long long m = __ballot(it.kept);
-        const int o = run + __popcll(m & ((1ull << lane) - 1ull));
+        const int o = run + pxd_ballot_rank(m, lane);
         if (it.kept && o < cap) {                       // 0 <= o: the kept items in front of this one
             out_pos[o] = it.pos;
             out_charge[o] = (uint8_t)it.q;
@@ -225,16 +209,7 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_overlay_write_kernel(OvStore 
         run += __popcll(m);
         // the starts of the pairs that begin in this step: pair e of a first item (kept, so o is its index) and the empty pairs directly in
         // front of it, [f, e) with U[f] == ... == U[e] == t; f = the first entry of U[0 .. E] that is >= t
-        int f = it.e;
-        if (it.first) {
-            int lo = 0, hi = it.e;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (U[mid] < (int)t) lo = mid + 1;
-                else hi = mid;
-            }
-            f = lo;
-        }
+        const int f = it.first ? cl_lower_bound(U, it.e, (int)t) : it.e;
         unsigned long long firsts = __ballot(it.first);
         while (firsts) {                                // wave-uniform
             const int src = __ffsll(firsts) - 1;
@@ -250,16 +225,15 @@ extern "C" long ieagan_pxd_event_overlay_scratch(int E, long capacity) {
     return (long)E + 1 + (long)PXD_WAVES * ov_blocks(pxd_cap(capacity));
 }
 
-static int ov_check_store(const char* side, const int* pos, const unsigned char* charge, const long* offsets, long digits, int events,
-                          const int* ids) {
-    const char* who = "pxd_event_overlay";
+// One store; `names` are its arguments in the error texts: pos / charge, pos, offsets, ids.
+static int ov_check_store(const char* who, const char* side, const char* const names[4], const int* pos, const unsigned char* charge,
+                          const long* offsets, long digits, int events, const int* ids) {
     CHECK_ARG(digits >= 0 && events >= 0, "%s: %s_digits = %ld / %s_events = %d is negative", who, side, digits, side, events);
-    CHECK_ARG(digits == 0 || (pos != nullptr && charge != nullptr), "%s: %s_pos / %s_charge is NULL with %ld digits", who, side, side, digits);
-    CHECK_ARG(((uintptr_t)pos & 3u) == 0, "%s: %s_pos is not 4-byte aligned", who, side);
-    CHECK_ARG(events == 0 || offsets != nullptr, "%s: %s_offsets is NULL with %d events", who, side, events);
-    CHECK_ARG(((uintptr_t)offsets & 7u) == 0, "%s: %s_offsets is not 8-byte aligned", who, side);
-    CHECK_ARG(ids != nullptr && ((uintptr_t)ids & 3u) == 0, "%s: %s_ids is NULL or misaligned", who, side);
-    return 0;
+    if (int rc = pxd_check_arrays(who, names[0], "digits", digits, {pos, charge})) return rc;
+    if (int rc = pxd_check_aligned(who, names[1], 4, {pos})) return rc;
+    if (int rc = pxd_check_arrays(who, names[2], "events", events, {offsets})) return rc;
+    if (int rc = pxd_check_aligned(who, names[2], 8, {offsets})) return rc;
+    return pxd_check_totals(who, names[3], {ids});
 }
 
 extern "C" int ieagan_pxd_event_overlay(const int* a_pos, const unsigned char* a_charge, const long* a_offsets, long a_digits, int a_events,
@@ -268,16 +242,17 @@ extern "C" int ieagan_pxd_event_overlay(const int* a_pos, const unsigned char* a
                                         unsigned char* out_charge, long* out_offsets, int* scratch, void* stream) {
     const char* who = "pxd_event_overlay";
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = ov_check_store("a", a_pos, a_charge, a_offsets, a_digits, a_events, a_ids)) return rc;
-    if (int rc = ov_check_store("b", b_pos, b_charge, b_offsets, b_digits, b_events, b_ids)) return rc;
+    static const char* const a_names[4] = {"a_pos / a_charge", "a_pos", "a_offsets", "a_ids"};
+    static const char* const b_names[4] = {"b_pos / b_charge", "b_pos", "b_offsets", "b_ids"};
+    if (int rc = ov_check_store(who, "a", a_names, a_pos, a_charge, a_offsets, a_digits, a_events, a_ids)) return rc;
+    if (int rc = ov_check_store(who, "b", b_names, b_pos, b_charge, b_offsets, b_digits, b_events, b_ids)) return rc;
     CHECK_ARG(E > 0 && E <= 65535, "%s: E = %d pairs outside 1 .. 65535", who, E);
     if (int rc = pxd_check_geometry(who, S, H, W, true)) return rc;         // S * H * W < 2^31: the positions of an event fit int32
-    CHECK_ARG(capacity >= 0, "%s: capacity = %ld is negative", who, capacity);
-    CHECK_ARG(capacity == 0 || (out_pos != nullptr && out_charge != nullptr), "%s: out_pos / out_charge is NULL with capacity %ld", who, capacity);
-    CHECK_ARG(((uintptr_t)out_pos & 3u) == 0, "%s: out_pos is not 4-byte aligned", who);
-    CHECK_ARG(out_offsets != nullptr && ((uintptr_t)out_offsets & 7u) == 0, "%s: out_offsets is NULL or not 8-byte aligned", who);
-    CHECK_ARG(scratch != nullptr && ((uintptr_t)scratch & 3u) == 0,
-              "%s: scratch (ieagan_pxd_event_overlay_scratch int32 words) is NULL or misaligned", who);
+    if (int rc = pxd_check_capacity(who, "capacity", capacity)) return rc;
+    if (int rc = pxd_check_arrays(who, "out_pos / out_charge", "capacity", capacity, {out_pos, out_charge})) return rc;
+    if (int rc = pxd_check_aligned(who, "out_pos", 4, {out_pos})) return rc;
+    if (int rc = pxd_check_needed(who, "out_offsets", 8, {out_offsets})) return rc;
+    if (int rc = pxd_check_needed(who, "scratch (ieagan_pxd_event_overlay_scratch int32 words)", 4, {scratch})) return rc;
     const int cap = pxd_cap(capacity);
     const int Bk = ov_blocks(cap);
     const OvStore A = {a_pos, (const uint8_t*)a_charge, a_offsets, a_digits, a_events, a_ids};

@@ -14,7 +14,7 @@
 //            wave's own slot; counts[n] = 0.
 //   moments  wave g owns the digits [g * chunk, (g + 1) * chunk).  Digits ascend in flat index, so the 64 digits of a step fall into few
 //            runs of equal label: a segmented sum over each run (shuffles), then one 64-bit integer atomic add per run and moment.
-//   scan     pxd_scan_slots over the wave slots, in place; writes total.
+//   scan     pxd_scan_slots over the wave slots, in place; writes total (pxd_scan_total_kernel).
 //   compact  the partition of init: rank of an accepted cluster = base[slot] + accepted ones of the wave's earlier steps + accepted ones in
 //            the lower lanes (ballot).  Writes cluster / u / v at the rank; counts[n] += accepted clusters of image n, one integer atomic
 //            per image and step.  No atomic decides a position.
@@ -26,8 +26,6 @@
 #define PXD_MAP_U 25
 #define PXD_MAP_V 48
 
-typedef unsigned long long u64;
-
 __device__ __forceinline__ bool reco_accept(const uint8_t* __restrict__ seed, const int* __restrict__ ccharge, int j, int seed_cut,
                                             int charge_cut) {
     return (int)seed[j] >= seed_cut && ccharge[j] >= charge_cut;
@@ -37,37 +35,28 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_reco_init_kernel(const uint8_
                                                                     const int* __restrict__ ctotal, int cap, int chunk, int seed_cut,
                                                                     int charge_cut, int N, u64* __restrict__ mu, u64* __restrict__ mv,
                                                                     int* __restrict__ counts, int* __restrict__ slots) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
-    const long T = max(min(ctotal[0], cap), 0);
-    const long j0 = (long)g * chunk;
-    const long j1 = j0 + chunk < T ? j0 + chunk : T;
+    const PxdWaveRange w(pxd_total(ctotal, cap), chunk);
     int accepted = 0;
-    for (long jj = j0 + lane; jj < j1; jj += 64) {
+    for (long jj = w.k0 + w.lane; jj < w.k1; jj += 64) {
         const int j = (int)jj;
         mu[j] = 0ull;
         mv[j] = 0ull;
         accepted += (int)reco_accept(seed, ccharge, j, seed_cut, charge_cut);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) accepted += __shfl_xor(accepted, o, 64);
-    if (lane == 0) slots[g] = accepted;
-    for (int n = blockIdx.x * PXD_THREADS + threadIdx.x; n < N; n += gridDim.x * PXD_THREADS) counts[n] = 0;
+    accepted = pxd_wave_sum(accepted);
+    if (w.lane == 0) slots[w.g] = accepted;
+    for (int n = pxd_grid_thread(); n < N; n += pxd_grid_threads()) counts[n] = 0;
 }
 
 __global__ __launch_bounds__(PXD_THREADS) void pxd_reco_moments_kernel(const int* __restrict__ index, const uint8_t* __restrict__ charge,
                                                                        const int* __restrict__ label, const int* __restrict__ dtotal,
                                                                        const int* __restrict__ ctotal, int cap, int chunk, int HW, int W,
                                                                        u64* __restrict__ mu, u64* __restrict__ mv) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
-    const long M = min(dtotal[0], cap);
-    const int T = min(ctotal[0], cap);
-    const long k0 = (long)g * chunk;
-    const long k1 = k0 + chunk < M ? k0 + chunk : M;
-    for (long kb = k0; kb < k1; kb += 64) {         // wave-uniform bounds
-        const long kk = kb + lane;
-        const int k = (int)kk;
-        int lab = kk < k1 ? label[k] : -1;
-        if ((unsigned)lab >= (unsigned)T) lab = -1;         // no digit, or not a row of the table: adds nothing
+    const PxdWaveRange w(pxd_total(dtotal, cap), chunk);
+    const int T = pxd_total(ctotal, cap), lane = w.lane;
+    for (long kb = w.k0; kb < w.k1; kb += 64) {
+        const int k = (int)(kb + lane);
+        const int lab = pxd_digit_label(label, kb + lane, w.k1, T);         // -1 adds nothing
         u64 qr = 0ull, qc = 0ull;
         if (lab >= 0) {
             int r, c;
@@ -86,32 +75,24 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_reco_moments_kernel(const int
     }
 }
 
-// The prefix sum of pxd_common.h over the wave slots of the init launch (groups <= CL_MAX_BLOCKS: one tile); writes total.
-__global__ __launch_bounds__(PXD_SCAN_THREADS) void pxd_reco_scan_kernel(int* __restrict__ slots, int groups, int* __restrict__ total) {
-    const int all = pxd_scan_slots(slots, groups);
-    if (threadIdx.x == 0) total[0] = all;
-}
-
 __global__ __launch_bounds__(PXD_THREADS) void pxd_reco_compact_kernel(const int* __restrict__ first, const int* __restrict__ ccharge,
                                                                        const uint8_t* __restrict__ seed, const int* __restrict__ ctotal,
                                                                        int cap, int chunk, int seed_cut, int charge_cut, int N, int HW,
                                                                        const u64* __restrict__ mu, const u64* __restrict__ mv,
                                                                        const int* __restrict__ slots, int* __restrict__ cluster,
                                                                        float* __restrict__ u, float* __restrict__ v, int* counts) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * PXD_WAVES + (threadIdx.x >> 6);
-    const long T = max(min(ctotal[0], cap), 0);
-    const long j0 = (long)g * chunk;
-    const long j1 = j0 + chunk < T ? j0 + chunk : T;
-    int run = slots[g];
-    for (long jb = j0; jb < j1; jb += 64) {         // wave-uniform bounds
+    const PxdWaveRange w(pxd_total(ctotal, cap), chunk);
+    const int lane = w.lane;
+    int run = slots[w.g];
+    for (long jb = w.k0; jb < w.k1; jb += 64) {
         const long jj = jb + lane;
         const int j = (int)jj;
-        const bool ok = jj < j1 && reco_accept(seed, ccharge, j, seed_cut, charge_cut);
+        const bool ok = jj < w.k1 && reco_accept(seed, ccharge, j, seed_cut, charge_cut);
         const u64 m = __ballot(ok);
         if (m == 0ull) continue;
         int n = -1;
         if (ok) {                                   // accepted <= clusters <= capacity: the rank is inside every array
-            const int a = run + __popcll(m & ((1ull << lane) - 1ull));
+            const int a = run + pxd_ballot_rank(m, lane);
             const double q = (double)ccharge[j];
             cluster[a] = j;
             u[a] = (float)((double)mu[j] / q);
@@ -137,12 +118,12 @@ __global__ __launch_bounds__(PXD_THREADS) void pxd_cluster_maps_kernel(const int
                                                                        const int* __restrict__ ctotal, const int* __restrict__ dtotal, int cap,
                                                                        int H, int W, int n_sensors, u64* __restrict__ count,
                                                                        u64* __restrict__ charge, u64* __restrict__ overflow) {
-    const int t0 = blockIdx.x * PXD_THREADS + threadIdx.x;
+    const int t0 = pxd_grid_thread();
     if (t0 == 0 && dtotal[0] > cap) atomicAdd(overflow, 1ull);
-    const int T = min(ctotal[0], cap);
-    const int A = min(atotal[0], T);
+    const int T = pxd_total(ctotal, cap);
+    const int A = pxd_total(atotal, T);
     const int HW = H * W;
-    for (int a = t0; a < A; a += gridDim.x * PXD_THREADS) {
+    for (int a = t0; a < A; a += pxd_grid_threads()) {
         const int j = cluster[a];
         if ((unsigned)j >= (unsigned)T) continue;           // not a row of the table
         const int q = ccharge[j], f = first[j];
@@ -167,37 +148,31 @@ extern "C" int ieagan_pxd_cluster_positions(const int* index, const unsigned cha
                                             unsigned long long* mv, int* cluster, float* u, float* v, int* counts, int* total, int* scratch,
                                             void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = pxd_check_geometry("pxd_cluster_positions", N, H, W, true)) return rc;
-    CHECK_ARG((double)H * W * 255.0 < 2147483648.0, "pxd_cluster_positions: H * W * 255 = %d * %d * 255 does not fit the int32 cluster charge", H, W);
-    CHECK_ARG(capacity >= 0, "pxd_cluster_positions: capacity = %ld is negative", capacity);
-    CHECK_ARG(seed_cut >= 0 && charge_cut >= 0, "pxd_cluster_positions: seed_cut = %d / charge_cut = %d is negative", seed_cut, charge_cut);
-    CHECK_ARG(digit_total != nullptr && cluster_total != nullptr && (((uintptr_t)digit_total | (uintptr_t)cluster_total) & 3u) == 0,
-              "pxd_cluster_positions: digit_total / cluster_total is NULL or misaligned");
-    CHECK_ARG(capacity == 0 || (index != nullptr && charge != nullptr && label != nullptr),
-              "pxd_cluster_positions: index / charge / label is NULL with capacity %ld", capacity);
-    CHECK_ARG(capacity == 0 || (first != nullptr && ccharge != nullptr && seed != nullptr),
-              "pxd_cluster_positions: a cluster table is NULL with capacity %ld", capacity);
-    CHECK_ARG(capacity == 0 || (mu != nullptr && mv != nullptr && cluster != nullptr && u != nullptr && v != nullptr),
-              "pxd_cluster_positions: an output array is NULL with capacity %ld", capacity);
-    CHECK_ARG((((uintptr_t)index | (uintptr_t)label | (uintptr_t)first | (uintptr_t)ccharge | (uintptr_t)cluster | (uintptr_t)u | (uintptr_t)v) &
-               3u) == 0, "pxd_cluster_positions: an int32 / fp32 array is not 4-byte aligned");
-    CHECK_ARG((((uintptr_t)mu | (uintptr_t)mv) & 7u) == 0, "pxd_cluster_positions: mu / mv is not 8-byte aligned");
-    CHECK_ARG(counts != nullptr && total != nullptr && (((uintptr_t)counts | (uintptr_t)total) & 3u) == 0,
-              "pxd_cluster_positions: counts / total is NULL or misaligned");
-    CHECK_ARG(scratch != nullptr && ((uintptr_t)scratch & 3u) == 0,
-              "pxd_cluster_positions: scratch (ieagan_pxd_cluster_positions_scratch int32 words) is NULL or misaligned");
+    const char* who = "pxd_cluster_positions";
+    if (int rc = pxd_check_geometry(who, N, H, W, true)) return rc;
+    if (int rc = pxd_check_cluster_charge(who, H, W)) return rc;
+    if (int rc = pxd_check_capacity(who, "capacity", capacity)) return rc;
+    CHECK_ARG(seed_cut >= 0 && charge_cut >= 0, "%s: seed_cut = %d / charge_cut = %d is negative", who, seed_cut, charge_cut);
+    if (int rc = pxd_check_totals(who, "digit_total / cluster_total", {digit_total, cluster_total})) return rc;
+    if (int rc = pxd_check_arrays(who, "index / charge / label", "capacity", capacity, {index, charge, label})) return rc;
+    if (int rc = pxd_check_arrays(who, "a cluster table", "capacity", capacity, {first, ccharge, seed})) return rc;
+    if (int rc = pxd_check_arrays(who, "an output array", "capacity", capacity, {mu, mv, cluster, u, v})) return rc;
+    if (int rc = pxd_check_aligned(who, "an int32 / fp32 array", 4, {index, label, first, ccharge, cluster, u, v})) return rc;
+    if (int rc = pxd_check_aligned(who, "mu / mv", 8, {mu, mv})) return rc;
+    if (int rc = pxd_check_needed(who, "counts / total", 4, {counts, total})) return rc;
+    if (int rc = pxd_check_needed(who, "scratch (ieagan_pxd_cluster_positions_scratch int32 words)", 4, {scratch})) return rc;
     const int cap = pxd_cap(capacity);
     const int HW = H * W;
     const int B = cl_blocks(cap), chunk = cl_chunk(cap, B);
     int* slots = scratch;
-    ProfScope prof("pxd_cluster_positions", 0.0, 0.0, st);
+    ProfScope prof(who, 0.0, 0.0, st);
     hipLaunchKernelGGL(pxd_reco_init_kernel, dim3(B), dim3(PXD_THREADS), 0, st, (const uint8_t*)seed, ccharge, cluster_total, cap, chunk, seed_cut,
                        charge_cut, N, mu, mv, counts, slots);
     CHECK_LAUNCH("pxd_cluster_positions init");
     hipLaunchKernelGGL(pxd_reco_moments_kernel, dim3(B), dim3(PXD_THREADS), 0, st, index, (const uint8_t*)charge, label, digit_total, cluster_total,
                        cap, chunk, HW, W, mu, mv);
     CHECK_LAUNCH("pxd_cluster_positions moments");
-    hipLaunchKernelGGL(pxd_reco_scan_kernel, dim3(1), dim3(PXD_SCAN_THREADS), 0, st, slots, B, total);
+    hipLaunchKernelGGL(pxd_scan_total_kernel<PXD_SCAN_THREADS>, dim3(1), dim3(PXD_SCAN_THREADS), 0, st, slots, B, total);
     CHECK_LAUNCH("pxd_cluster_positions scan");
     hipLaunchKernelGGL(pxd_reco_compact_kernel, dim3(B), dim3(PXD_THREADS), 0, st, first, ccharge, (const uint8_t*)seed, cluster_total, cap, chunk,
                        seed_cut, charge_cut, N, HW, (const u64*)mu, (const u64*)mv, (const int*)slots, cluster, u, v, counts);
@@ -210,22 +185,18 @@ extern "C" int ieagan_pxd_cluster_maps(const int* cluster, const int* accepted_t
                                        const int* digit_total, int N, int H, int W, int n_sensors, long capacity, unsigned long long* count,
                                        unsigned long long* charge, unsigned long long* overflow, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = pxd_check_geometry("pxd_cluster_maps", N, H, W, true)) return rc;
-    CHECK_ARG((double)H * W * 255.0 < 2147483648.0, "pxd_cluster_maps: H * W * 255 = %d * %d * 255 does not fit the int32 cluster charge", H, W);
-    CHECK_ARG(n_sensors > 0 && N % n_sensors == 0, "pxd_cluster_maps: N = %d is not a multiple of n_sensors = %d", N, n_sensors);
-    CHECK_ARG(capacity >= 0, "pxd_cluster_maps: capacity = %ld is negative", capacity);
-    CHECK_ARG(capacity == 0 || (cluster != nullptr && first != nullptr && ccharge != nullptr && mu != nullptr && mv != nullptr),
-              "pxd_cluster_maps: cluster / first / ccharge / mu / mv is NULL with capacity %ld", capacity);
-    CHECK_ARG((((uintptr_t)cluster | (uintptr_t)first | (uintptr_t)ccharge) & 3u) == 0 && (((uintptr_t)mu | (uintptr_t)mv) & 7u) == 0,
-              "pxd_cluster_maps: an int32 array is not 4-byte or mu / mv not 8-byte aligned");
-    CHECK_ARG(accepted_total != nullptr && cluster_total != nullptr && digit_total != nullptr &&
-              (((uintptr_t)accepted_total | (uintptr_t)cluster_total | (uintptr_t)digit_total) & 3u) == 0,
-              "pxd_cluster_maps: accepted_total / cluster_total / digit_total is NULL or misaligned");
-    CHECK_ARG(count != nullptr && charge != nullptr && overflow != nullptr &&
-              (((uintptr_t)count | (uintptr_t)charge | (uintptr_t)overflow) & 7u) == 0,
-              "pxd_cluster_maps: count / charge / overflow is NULL or not 8-byte aligned");
+    const char* who = "pxd_cluster_maps";
+    if (int rc = pxd_check_geometry(who, N, H, W, true)) return rc;
+    if (int rc = pxd_check_cluster_charge(who, H, W)) return rc;
+    if (int rc = pxd_check_whole_events(who, N, n_sensors)) return rc;
+    if (int rc = pxd_check_capacity(who, "capacity", capacity)) return rc;
+    if (int rc = pxd_check_arrays(who, "cluster / first / ccharge / mu / mv", "capacity", capacity, {cluster, first, ccharge, mu, mv})) return rc;
+    if (int rc = pxd_check_aligned(who, "an int32 array", 4, {cluster, first, ccharge})) return rc;
+    if (int rc = pxd_check_aligned(who, "mu / mv", 8, {mu, mv})) return rc;
+    if (int rc = pxd_check_totals(who, "accepted_total / cluster_total / digit_total", {accepted_total, cluster_total, digit_total})) return rc;
+    if (int rc = pxd_check_needed(who, "count / charge / overflow", 8, {count, charge, overflow})) return rc;
     const int cap = pxd_cap(capacity);
-    ProfScope prof("pxd_cluster_maps", 0.0, 0.0, st);
+    ProfScope prof(who, 0.0, 0.0, st);
     hipLaunchKernelGGL(pxd_cluster_maps_kernel, dim3(cl_blocks(cap)), dim3(PXD_THREADS), 0, st, cluster, accepted_total, first, ccharge,
                        (const u64*)mu, (const u64*)mv, cluster_total, digit_total, cap, H, W, n_sensors, (u64*)count, (u64*)charge, (u64*)overflow);
     CHECK_LAUNCH("pxd_cluster_maps");
