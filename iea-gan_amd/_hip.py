@@ -19,7 +19,7 @@ CONV_FORCE_WS64 = 32     # ieagan_conv_desc.flags bit (tests / benchmarks): conv
 CONV_NO_WS64 = 16        # ieagan_conv_desc.flags bit (tests / benchmarks): C = 64 3x3 layers through conv3x3_lds instead of conv3x3_ws64
 CONV_NO_LDS_WEIGHTS = 2  # ieagan_conv_desc.flags bit: C = 64 / 128 3x3 layers through conv3x3_halo instead of conv3x3_lds
 CONV_FORCE_GATHER = 1   # ieagan_conv_desc.flags bit (tests): route a 3x3 layer through the gather kernel
-B1_OCC2, B1_OCC3, B1_TP32 = 1, 2, 4  # ieagan_conv1x1_bwd_desc.flags bits (benchmarks)
+B1_TP32 = 4  # ieagan_conv1x1_bwd_desc.flags bit (benchmarks): 32-pixel wave tiles everywhere
 BWD_NO_REDUCE = 16      # ieagan_conv1x1_bwd / ieagan_conv3x3_bwd: the caller folds the dW slabs (ieagan_wgrad_reduce)
 PXD_BINS = 251          # bins of the ADC spectrum of ieagan_pxd_stats (csrc/pxd_stats.hip)
 # columns of one sensor's row of the ieagan_pxd_cluster_stats tables (csrc/pxd_clusters.hip): name -> (first column, bins)

@@ -142,16 +142,9 @@ __global__ void selftest_tr_kernel(const bf16* __restrict__ in, bf16* __restrict
     for (int i = l; i < 64 * 16; i += 64) lds[i] = in[i];
     __syncthreads();
     const int lr = l & 15, lg = l >> 4;
-    const int q = lr >> 2, p = lr & 3;
-    const bf16* p0 = lds + (8 * lg + q) * 16 + 4 * p;
-    const bf16* p1 = p0 + 4 * 16;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p0);
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p1);
+    const bf16x8 f = tr_frag(lds, 16, 8 * lg, 4, 0, lr);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        out[l * 8 + j] = lo[j];
-        out[l * 8 + 4 + j] = hi[j];
-    }
+    for (int j = 0; j < 8; ++j) out[l * 8 + j] = f[j];
 }
 
 extern "C" int ieagan_selftest_tr_read(const void* in, void* out, void* stream) {

@@ -27,15 +27,7 @@ __device__ __forceinline__ bf16x8 pack2(const f32x4& a, const f32x4& b) {
 
 // B fragment for k-slots pi(g, .) and columns [c0, c0+16) of an LDS tile [rows][stride] (bf16, natural layout)
 __device__ __forceinline__ bf16x8 trfrag(const bf16* tile, int stride, int c0, int lr, int lg) {
-    const int q = lr >> 2, p = lr & 3;
-    const bf16* p0 = tile + (4 * lg + q) * stride + c0 + 4 * p;
-    const bf16* p1 = p0 + 16 * stride;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p0);
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p1);
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
+    return tr_frag(tile, stride, 4 * lg, 16, c0, lr);
 }
 
 // Swizzled LDS tiles (backward kernels): the 16-byte chunk c of row r of a [32][W] tile lives at chunk position c ^ key(r), with
@@ -52,13 +44,7 @@ __device__ __forceinline__ bf16x8 trfrag_swz(const bf16* tile, int c0, int lr, i
     const int q = lr >> 2, p = lr & 3;
     const int row = 4 * lg + q;                                   // rows row and row + 16 share the key
     const bf16* p0 = tile + swz_off<W>(row, (c0 >> 3) + (p >> 1)) + 4 * (p & 1);
-    const bf16* p1 = p0 + 16 * W;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p0);
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p1);
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
+    return tr_pair(p0, p0 + 16 * W);
 }
 
 // 8 consecutive features [8g, 8g+8) of row `row` of a [rows][width] bf16 matrix (zero beyond rows / width)

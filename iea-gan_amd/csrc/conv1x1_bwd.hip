@@ -20,33 +20,16 @@
 // are folded through LDS atomics and leave the block as ONE slab store (two-stage accumulation) or one round of global atomics.
 #include "common.h"
 #include "conv_args.h"
-#include "conv_common.h"
+#include "conv_bwd.h"
 #include <stdio.h>
 
 typedef ieagan_conv1x1_bwd_desc Bwd1Args;
-
-
-__host__ __device__ constexpr int b1_stride(int C) { return ((C / 16) % 2 == 0) ? C + 16 : C; }      // elements; odd multiple of 32 bytes
-
-// K(pixel)-major fragment: rows pix0 .. pix0+3 and pix0+8 .. pix0+11 of column (col0 + lr) of a [pixel][channel] 16-bit LDS image
-// (see conv_wgrad.hip: frag_T).  EXEC must be all ones.
-__device__ __forceinline__ bf16x8 b1_frag_T(const bf16* lds, int stride_elems, int pix0, int col0, int lr) {
-    const int q = lr >> 2, p = lr & 3;
-    const bf16* p0 = lds + (pix0 + q) * stride_elems + col0 + 4 * p;
-    const bf16* p1 = p0 + 8 * stride_elems;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p0);
-    const bf16x4 hh = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p1);
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hh[0]; f[5] = hh[1]; f[6] = hh[2]; f[7] = hh[3];
-    return f;
-}
 
 // TP: conv-resolution pixels per wave tile (32 or 64).  64 keeps twice the bytes in flight per wave -- these launches wait on memory
 // (rocprofv3: 40-70 % of the wave cycles parked in s_waitcnt at two waves per SIMD) -- where the LDS tiles of two blocks still fit a CU.
 template <int CIN, int COUT, int RS, bool AFF, int TP>
 struct B1Cfg {
-    static constexpr int GS = b1_stride(COUT), XS = b1_stride(CIN);
+    static constexpr int GS = lds_stride_odd32(COUT), XS = lds_stride_odd32(CIN);
     static constexpr int CPG = COUT / 8, CPX = CIN / 8;           // 16-byte chunks per pixel
     static constexpr int GCH = TP * CPG / 64;                   // g chunks per lane and tile
     static constexpr int XIT = TP * CPX / 64;                   // x items per lane and tile (an item = one chunk; 2x2 chunks when pooled)
@@ -76,12 +59,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 15, lg = lane >> 4;
     const int H = a.H, W = a.W, HW = H * W;
-    // XCD-aware order: blocks b and b + 8 share an XCD (and its L2): every XCD walks one contiguous run of tiles
-    int bid = blockIdx.x;
-    {
-        const int q = nblk / 8, r = nblk % 8, xcd = bid % 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
+    const int bid = xcd_block_order(blockIdx.x, nblk);               // every XCD walks one contiguous run of tiles
     const int n = bid / bpi;                                      // a block stays inside ONE image (per-image BatchNorm accumulators)
     const int t0 = (bid - n * bpi) * tpb;
     const int t1 = min(t0 + tpb, tpi);
@@ -95,21 +73,14 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
     const int lmode = a.lg != nullptr ? a.lmode : -1;
 
     // ---- block prologue: BatchNorm table of this image, dgrad weight fragments, effgrad terms of this lane's g chunk
-    if (AFF) {
+    if (AFF) {                                                     // (stage_bn_rows of conv_bwd.h, in place: the helper orders the two loads the other way)
         for (int i = threadIdx.x; i < CIN; i += 256) {
             aff_s[i] = a.src.scale[(long)n * a.src.aff_nstride + i];
             aff_s[CIN + i] = a.src.shift[(long)n * a.src.aff_nstride + i];
         }
     }
-    if (eff) {
-        const int ev = (a.n_per_event > 0) ? n / a.n_per_event : 0;
-        for (int i = threadIdx.x; i < COUT; i += 256) {
-            eff_s[i] = a.dstat[(long)ev * 2 * COUT + i];
-            eff_s[COUT + i] = 2.f * a.dstat[(long)ev * 2 * COUT + COUT + i];
-        }
-    }
+    if (eff) stage_eff_rows(eff_s, a.dstat, n, a.n_per_event, COUT);
     __syncthreads();
-    typedef const __attribute__((address_space(3))) float* lds_cf;
     bf16x8 bfrag[K::KS_D][K::NT_D];                               // B[k = cout][col = cin]: rows of the transposed pack [Cin][Kpad2]
 #pragma unroll
     for (int ks = 0; ks < K::KS_D; ++ks)
@@ -119,7 +90,6 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
             bfrag[ks][nt] = (k < COUT) ? *(const bf16x8*)((const bf16*)a.w_bwd + (long)(nt * 16 + lr) * a.Kpad2 + k) : zero8();
         }
     const int ccg = lane % K::CPG, ccx = lane % K::CPX;          // this lane's channel chunk in g / in x (fixed over its items)
-    typedef const __attribute__((address_space(3))) f32x4* lds_cf4;
     const float* dsl = eff_s + ccg * 8;                           // {dsum, 2 dsumsq} rows of this lane's g chunk (LDS)
     float s1[8], s2[8];
 #pragma unroll
@@ -182,10 +152,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
             const int px = (j * 64 + lane) / K::CPG;
             bf16x8 wv = rg[j];
             if (eff) {
-                const f32x4 d0 = *(lds_cf4)(dsl), d1 = *(lds_cf4)(dsl + 4), q0 = *(lds_cf4)(dsl + COUT), q1 = *(lds_cf4)(dsl + COUT + 4);
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    wv[i] = f2bf(bf2f(rg[j][i]) + (i < 4 ? d0[i & 3] : d1[i & 3]) + bf2f(ry[j][i]) * (i < 4 ? q0[i & 3] : q1[i & 3]));
+                wv = effgrad8(rg[j], ry[j], dsl, COUT);
                 if (a.geff_out != nullptr) *(bf16x8*)((bf16*)a.geff_out + (p0 + px) * COUT + ccg * 8) = wv;
             }
             *(bf16x8*)(lds_g + px * K::GS + ccg * 8) = wv;
@@ -229,8 +196,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
             }
         }
         if (t + 4 < t1) request(t + 4);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_fence();
         // ---- 3. weight gradient (+ bias column sums): one K step of 32 pixels
         if (want_w) {
 #pragma unroll
@@ -238,10 +204,10 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
             const int pix0 = kk * 32 + (lg >> 1) * 16 + (lg & 1) * 4;
             bf16x8 afr[K::MT_W];
 #pragma unroll
-            for (int mt = 0; mt < K::MT_W; ++mt) afr[mt] = b1_frag_T(lds_g, K::GS, pix0, mt * 16, lr);
+            for (int mt = 0; mt < K::MT_W; ++mt) afr[mt] = tr_frag(lds_g, K::GS, pix0, 8, mt * 16, lr);
 #pragma unroll
             for (int nj = 0; nj < K::NJ_W; ++nj) {
-                bf16x8 b = b1_frag_T(lds_x, K::XS, pix0, nj * 16, lr);
+                bf16x8 b = tr_frag(lds_x, K::XS, pix0, 8, nj * 16, lr);
                 if (RS == 0) {                                    // forward prologue on the fragment: 8 pixels of channel nj*16 + lr
                     if (AFF) {
                         const float sc = *(lds_cf)(aff_s + nj * 16 + lr), sh = *(lds_cf)(aff_s + CIN + nj * 16 + lr);
@@ -285,8 +251,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
 #pragma unroll
                         for (int r = 0; r < 4; ++r) wlds[(ms * 16 + lg * 4 + r) * K::LDW + nt * 16 + lr] = acc[nt][r];
                 }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();
 #pragma unroll
                 for (int it = 0; it < K::EIT; ++it) {
                     const int j = ep * K::EIT + it;               // == the staging item index of this (lane, it)
@@ -309,6 +274,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
                     }
                     if (a.out_mode == 0 && (AFF || relu)) {
                         const bf16x8 xv = *(const bf16x8*)(lds_x + px * K::XS + ccx * 8);        // RS == 0: the raw x tile is still in LDS
+                        // (prologue_bwd8 of conv_bwd.h, kept in place: see the note at the block end)
                         f32x4 c0 = {1.f, 1.f, 1.f, 1.f}, c1 = c0, h0 = {0.f, 0.f, 0.f, 0.f}, h1 = h0;
                         if (AFF) {
                             c0 = *(lds_cf4)(aff_s + ccx * 8);
@@ -352,8 +318,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
                     for (int i = 0; i < 8; ++i) o[i] = f2bf(v[i]);
                     *(bf16x8*)((bf16*)a.dx + (p0 + px) * CIN + ccx * 8) = o;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // the next pass / tile overwrites the wave's buffers
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();      // the next pass / tile overwrites the wave's buffers
             }
         }
     }
@@ -361,16 +326,16 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
     // ---- block end: BatchNorm accumulators (sum d, sum d*x per image), then the fold of the four partial dW
     __syncthreads();
     if (AFF && a.bn_acc != nullptr) {
-        // fold the lanes that share a chunk through the (now free) LDS, one atomic per channel and block: same scheme as stats_flush
-        float* sx_all = (float*)smem;
+        // The scheme of bn_acc_flush (conv_bwd.h), kept in place together with the prologue backward above.  With -ffp-contract=fast the
+        // compiler decides per build which of the s2 += d * x become FMAs; through the shared helpers it decided differently for this
+        // kernel (4 of 8 moved), which changes the last bits of bn_acc.  conv3x3_bwd keeps its contraction with the helpers.
+        float* sx = (float*)smem + wave * STATS_SX_FLOATS;
         constexpr int CPP = K::CPX, SH = 64 / CPP;
-        float* sx = sx_all + wave * STATS_SX_FLOATS;
 #pragma unroll
         for (int w = 0; w < 2; ++w) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) sx[i * 64 + (lane ^ i)] = w ? s2[i] : s1[i];
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            wave_fence();
             if (lane < 8 * CPP) {
                 const int cc = lane % CPP, i = lane / CPP;
                 float tt = 0.f;
@@ -378,8 +343,7 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
                 for (int k = 0; k < SH; ++k) tt += sx[i * 64 + ((cc + CPP * k) ^ i)];
                 red[(wave * CIN + cc * 8 + i) * 2 + w] = tt;
             }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            wave_fence();
         }
         __syncthreads();
         const int tt = threadIdx.x;
@@ -428,7 +392,6 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_bwd_kernel(Bwd1Args a, int t
 // ------------------------------------------------------------------------------------------------
 struct B1Plan {
     int tpi, tpb, bpi, nblk, tp;
-    bool occ3;
     long ws_elems;
 };
 
@@ -439,9 +402,8 @@ static bool b1_shape_ok(int cin, int cout, int rs, bool aff) {
            (cin == 16 && cout == 32) || (cin == 32 && cout == 64) || (cin == 32 && cout == 32);
 }
 
-// blocks per CU (= waves per SIMD): three only where 168 registers hold the kernel without spills AND it measured faster
-// (measured at N = 40, tools/bwd1x1_bench.py: never faster than two blocks with 64-pixel tiles; kept for benchmarks, IEAGAN_B1_OCC3)
-static bool b1_occ3(int cin, int cout, int rs, bool aff) { return false; }
+// Two blocks per CU (= waves per SIMD) everywhere: three (168 registers, 32-pixel tiles) never measured faster at N = 40.
+#define B1_OCC 2
 // 64-pixel wave tiles where two blocks of four such waves still fit the 160 KB of a CU
 static int b1_tp(int cin, int cout, int rs) {
     if (rs == 2) return cin == 32 ? 64 : 32;           // (Cin = 16 keeps the raw 2x2 chunks in registers: spills at 64)
@@ -452,18 +414,15 @@ static int b1_plan(const Bwd1Args& a, B1Plan& p) {
     CHECK_ARG(a.src.rs == 0 || a.src.rs == 2, "conv1x1_bwd: resample mode %d", a.src.rs);
     CHECK_ARG(b1_shape_ok(a.Cin, a.Cout, a.src.rs, a.src.scale != nullptr), "conv1x1_bwd: shape %d -> %d (rs %d, affine %d) is not instantiated", a.Cin, a.Cout,
               a.src.rs, a.src.scale != nullptr);
-    const bool occ3 = (a.flags & IEAGAN_B1_OCC2) ? false : ((a.flags & IEAGAN_B1_OCC3) ? true : b1_occ3(a.Cin, a.Cout, a.src.rs, a.src.scale != nullptr));
-    int TP = (a.flags & IEAGAN_B1_TP32) || occ3 ? 32 : b1_tp(a.Cin, a.Cout, a.src.rs);
+    int TP = (a.flags & IEAGAN_B1_TP32) ? 32 : b1_tp(a.Cin, a.Cout, a.src.rs);
     if (a.W % TP != 0) TP = 32;                       // a tile must lie inside one row
     CHECK_ARG(a.W % TP == 0, "conv1x1_bwd: W %% 32 required (W = %d)", a.W);
     if (a.src.rs == 0) CHECK_ARG(a.H == a.src.Hs && a.W == a.src.Ws, "conv1x1_bwd: geometry mismatch");
     if (a.src.rs == 2) CHECK_ARG(2 * a.H == a.src.Hs && 2 * a.W == a.src.Ws, "conv1x1_bwd: pool geometry mismatch");
     CHECK_ARG(a.Kpad % 32 == 0 && a.Kpad >= a.Cin && a.Kpad2 % 32 == 0 && a.Kpad2 >= a.Cout, "conv1x1_bwd: bad weight-pack row lengths");
-    CHECK_ARG(a.Cg >= a.Cout && a.Cg % 8 == 0 && a.src.Cx >= a.Cin && a.src.Cx % 8 == 0, "conv1x1_bwd: bad channel strides");
-    CHECK_ARG((a.src.scale == nullptr) == (a.src.shift == nullptr), "conv1x1_bwd: scale / shift must come together");
-    CHECK_ARG((a.y == nullptr) == (a.dstat == nullptr), "conv1x1_bwd: the effgrad operands y / dstat must come together");
+    const int crc = bwd_common_checks("conv1x1_bwd", a.src, a.y, a.dstat, a.N, a.n_per_event, a.Cg, a.Cout, a.Cin);
+    if (crc != 0) return crc;
     CHECK_ARG(a.geff_out == nullptr || a.y != nullptr, "conv1x1_bwd: geff_out without effgrad");
-    CHECK_ARG(a.n_per_event >= 0 && (a.n_per_event == 0 || a.N % a.n_per_event == 0), "conv1x1_bwd: N is not a whole number of events");
     CHECK_ARG(a.out_mode == 0 || a.out_mode == 1, "conv1x1_bwd: out_mode");
     CHECK_ARG(a.out_mode == 0 || a.src.scale == nullptr, "conv1x1_bwd: plain da output cannot carry the BatchNorm backward");
     if (a.src.rs == 2 && a.dx != nullptr) CHECK_ARG(a.out_mode == 1 || a.Cin == 16, "conv1x1_bwd: dx at source resolution of a pooled source needs Cin = 16");
@@ -475,46 +434,25 @@ static int b1_plan(const Bwd1Args& a, B1Plan& p) {
         if (a.lmode == 2) CHECK_ARG(a.H % 2 == 0 && a.W % 2 == 0, "conv1x1_bwd: half-resolution shortcut gradient needs even H, W");
     }
     CHECK_ARG(a.dx != nullptr || a.dw != nullptr, "conv1x1_bwd: nothing to compute");
-    CHECK_ARG((a.flags & ~(IEAGAN_B1_OCC2 | IEAGAN_B1_OCC3 | IEAGAN_B1_TP32 | IEAGAN_BWD_NO_REDUCE)) == 0, "conv1x1_bwd: unknown flag bits 0x%x", a.flags);
+    CHECK_ARG((a.flags & ~(IEAGAN_B1_TP32 | IEAGAN_BWD_NO_REDUCE)) == 0, "conv1x1_bwd: unknown flag bits 0x%x", a.flags);
     CHECK_ARG(a.bn_slots >= 0, "conv1x1_bwd: bad bn_slots %d", a.bn_slots);
     CHECK_ARG(a.colsum == nullptr || a.dw != nullptr, "conv1x1_bwd: colsum rides on the weight gradient");
     const int tpi = a.H * a.W / TP;
-    // ONE round of persistent blocks: every resident slot (256 CUs x blocks per CU) gets one block, whole blocks per image, the four
-    // waves of a block interleave its tiles.  (A grid of 1040 blocks on 512 slots ran three rounds, the last one 3 % full.)
-    const int slots = 256 * (occ3 ? 3 : 2);
-    int bpi = slots / a.N;
-    if (bpi < 1) bpi = 1;
-    int tpb = (tpi + bpi - 1) / bpi;
-    tpb = (tpb + 3) / 4 * 4;
-    if (tpb < 8) tpb = 8;
-    bpi = (tpi + tpb - 1) / tpb;
+    const PersistentPlan pp = persistent_plan(tpi, a.N, B1_OCC, 8, 4);      // the four waves of a block interleave its tiles
     p.tp = TP;
-    p.occ3 = occ3;
     p.tpi = tpi;
-    p.tpb = tpb;
-    p.bpi = bpi;
-    p.nblk = bpi * a.N;
+    p.tpb = pp.tpb;
+    p.bpi = pp.bpi;
+    p.nblk = pp.nblk;
     const long direct_bytes = (long)p.nblk * a.Cout * a.Cin * 4;
     p.ws_elems = (a.dw != nullptr && direct_bytes >= (8L << 20)) ? (long)p.nblk * a.Cout * a.Kpad : 0;
     return 0;
 }
 
-extern "C" long ieagan_conv1x1_bwd_workspace(const ieagan_conv1x1_bwd_desc* d) {
-    B1Plan p;
-    if (d == nullptr || b1_plan(*d, p) != 0) return 0;
-    return p.ws_elems;
-}
-
-extern "C" int ieagan_conv1x1_bwd_slots(const ieagan_conv1x1_bwd_desc* d) {
-    B1Plan p;
-    if (d == nullptr) return IEAGAN_EINVAL;
-    const int rc = b1_plan(*d, p);
-    return rc != 0 ? rc : p.bpi;
-}
+extern "C" long ieagan_conv1x1_bwd_workspace(const ieagan_conv1x1_bwd_desc* d) { return bwd_plan_query<B1Plan>(d, b1_plan, false); }
+extern "C" int ieagan_conv1x1_bwd_slots(const ieagan_conv1x1_bwd_desc* d) { return (int)bwd_plan_query<B1Plan>(d, b1_plan, true); }
 
 extern "C" int ieagan_conv1x1_bwd_supported(int Cin, int Cout, int rs, int affine) { return b1_shape_ok(Cin, Cout, rs, affine != 0) ? 1 : 0; }
-
-int wgrad_reduce_launch(const float* part, float* dw, int S, int Cout, int Kpad, int K, hipStream_t st);      // conv_wgrad.hip
 
 extern "C" int ieagan_conv1x1_bwd(const ieagan_conv1x1_bwd_desc* d, void* stream) {
     CHECK_ARG(d != nullptr && d->g != nullptr && d->src.x != nullptr && d->w_bwd != nullptr, "conv1x1_bwd: null pointer");
@@ -538,12 +476,10 @@ extern "C" int ieagan_conv1x1_bwd(const ieagan_conv1x1_bwd_desc* d, void* stream
         snprintf(tag, sizeof(tag), "ci%d co%d %dx%d rs%d a%d r%d eff%d l%d w%d", a.Cin, a.Cout, a.H, a.W, a.src.rs, a.src.scale != nullptr, a.src.relu,
                  a.y != nullptr, a.lg ? a.lmode : -1, a.dw != nullptr);
     ProfScope prof("conv1x1_bwd", flops, bytes, st, tag, bytes_min);
-    const bool occ3 = p.occ3;
 #define B1_LAUNCH(CI, CO, RSV, AF)                                                                                                   \
     {                                                                                                                                \
-        if (occ3) hipLaunchKernelGGL((conv1x1_bwd_kernel<CI, CO, RSV, AF, 3, 32>), dim3(p.nblk), dim3(256), 0, st, a, p.tpi, p.tpb, p.bpi, p.nblk); \
-        else if (p.tp == 32) hipLaunchKernelGGL((conv1x1_bwd_kernel<CI, CO, RSV, AF, 2, 32>), dim3(p.nblk), dim3(256), 0, st, a, p.tpi, p.tpb, p.bpi, p.nblk); \
-        else hipLaunchKernelGGL((conv1x1_bwd_kernel<CI, CO, RSV, AF, 2, 64>), dim3(p.nblk), dim3(256), 0, st, a, p.tpi, p.tpb, p.bpi, p.nblk);      \
+        if (p.tp == 32) hipLaunchKernelGGL((conv1x1_bwd_kernel<CI, CO, RSV, AF, B1_OCC, 32>), dim3(p.nblk), dim3(256), 0, st, a, p.tpi, p.tpb, p.bpi, p.nblk); \
+        else hipLaunchKernelGGL((conv1x1_bwd_kernel<CI, CO, RSV, AF, B1_OCC, 64>), dim3(p.nblk), dim3(256), 0, st, a, p.tpi, p.tpb, p.bpi, p.nblk);      \
     }
 #define B1_CASE(CI, CO)                                                      \
     if (a.Cin == CI && a.Cout == CO) {                                       \

@@ -36,11 +36,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(ConvArgs a, int 
     // pixels then run at the same time on the same XCD and share the activations through its L2 -- as blockIdx.y they were whole
     // grid passes apart and every column streamed the input from memory again (5.7 GB per step over the 1x1 layers).
     const int gy = (a.Cout + 16 * NT - 1) / (16 * NT);
-    int bid = blockIdx.x;
-    {
-        const int tot = nblk * gy, q = tot / 8, r = tot % 8, xcd = bid % 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
+    int bid = xcd_block_order(blockIdx.x, nblk * gy);
     const int n_base = (bid % gy) * NT * 16;
     bid /= gy;
     // a block stays inside ONE statistics group (event; gpe pixel groups, bpe blocks): a single flush at its end
@@ -200,8 +196,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(ConvArgs a, int 
                 for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) wlds[(ms * 16 + lg * 4 + r) * LDW + nt * 16 + lr] = acc[ms][nt][r];
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            wave_fence();
 #pragma unroll
             for (int it = 0; it < ITER; ++it) {
                 const int row = (it * 64 + lane) / CPP;
@@ -251,8 +246,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(ConvArgs a, int 
                 }
                 *(bf16x8*)((bf16*)a.out + m * a.Cout + co0) = o;
             }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // the next pass overwrites the wave's buffer
-            __builtin_amdgcn_wave_barrier();
+            wave_fence();      // the next pass overwrites the wave's buffer
         }
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)

@@ -53,11 +53,7 @@ __global__ __launch_bounds__(256, 3) void conv1x1_tile_kernel(ConvArgs a) {
     // XCD-aware order with the n-tile column as the fast index (see conv1x1_stream.hip): the gy blocks that read the same 128 pixels
     // run side by side on one XCD and share them through its L2
     const int gy = a.Cout / (NT * 16);
-    int vid = blockIdx.x;
-    {
-        const int tot = gridDim.x, q = tot / 8, r = tot % 8, xcd = vid % 8;
-        vid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + vid / 8;
-    }
+    const int vid = xcd_block_order(blockIdx.x, gridDim.x);
     const int bx = vid / gy;
     const long m_blk = (long)bx * 128;
     const long m_base = m_blk + wave * 32;                    // this wave's 32 output pixels

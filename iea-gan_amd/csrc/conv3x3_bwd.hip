@@ -24,7 +24,7 @@
 // folds the slabs.  The per-image BatchNorm accumulators (sum d, sum d x) go to replica slot bid % 8 of the image.
 #include "common.h"
 #include "conv_args.h"
-#include "conv_common.h"
+#include "conv_bwd.h"
 #include <stdio.h>
 
 typedef ieagan_conv3x3_bwd_desc Bwd3Args;
@@ -35,8 +35,8 @@ typedef ieagan_conv3x3_bwd_desc Bwd3Args;
 template <int C>
 struct B3Cfg {
     static constexpr int NT = C / 16, CH = C / 8, CPP = CH;
-    static constexpr int PS = (C == 16) ? 32 : 96;                 // bytes per LDS pixel: an odd multiple of 32
-    static constexpr int PSE = PS / 2;
+    static constexpr int PSE = lds_stride_odd32(C);                // elements per LDS pixel
+    static constexpr int PS = 2 * PSE;                             // bytes: 32 / 96
     static constexpr int AW = B3_TW + 2, AH = B3_TH + 2;
     static constexpr int KP = ((9 * C + 31) / 32) * 32;            // 160 / 288
     static constexpr int KS = KP / 32;
@@ -54,42 +54,22 @@ struct B3Cfg {
     static_assert(4 * STATS_SX_FLOATS * 4 <= G_BYTES, "the statistics fold aliases the halo image");
 };
 
-// K(pixel)-major fragment (see conv_wgrad.hip: frag_T): rows pix0 .. pix0+3 and pix0+16 .. pix0+19 of column (col0 + lr).
-__device__ __forceinline__ bf16x8 b3_frag_T(const char* lds, int stride_bytes, int pix0, int col0, int lr) {
+// tr_frag (rows pix0 .. +3 and pix0+16 .. +19) for an x2 nearest-up-sampled operand kept as its SOURCE tile [4][16] pixels: conv columns
+// col0c + q and col0c + 16 + q of conv row 2*srow (+1) live at source pixel (srow, col >> 1)
+__device__ __forceinline__ bf16x8 b3_frag_T_up(const bf16* lds, int stride_elems, int srow, int col0c, int col0, int lr) {
     const int q = lr >> 2, p = lr & 3;
-    const char* p0 = lds + (pix0 + q) * stride_bytes + (col0 + 4 * p) * 2;
-    const char* p1 = p0 + 16 * stride_bytes;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p0);
-    const bf16x4 hh = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p1);
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hh[0]; f[5] = hh[1]; f[6] = hh[2]; f[7] = hh[3];
-    return f;
-}
-
-// the same for an x2 nearest-up-sampled operand kept as its SOURCE tile [4][16] pixels: conv columns col0c + q and col0c + 16 + q of conv
-// row 2*srow (+1) live at source pixel (srow, col >> 1)
-__device__ __forceinline__ bf16x8 b3_frag_T_up(const char* lds, int stride_bytes, int srow, int col0c, int col0, int lr) {
-    const int q = lr >> 2, p = lr & 3;
-    const char* p0 = lds + (srow * 16 + ((col0c + q) >> 1)) * stride_bytes + (col0 + 4 * p) * 2;
-    const char* p1 = p0 + 8 * stride_bytes;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p0);
-    const bf16x4 hh = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p1);
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hh[0]; f[5] = hh[1]; f[6] = hh[2]; f[7] = hh[3];
-    return f;
+    const bf16* p0 = lds + (srow * 16 + ((col0c + q) >> 1)) * stride_elems + col0 + 4 * p;
+    return tr_pair(p0, p0 + 8 * stride_elems);
 }
 
 // blocks per CU (= waves per SIMD): C = 16 -> 3 (168 registers), but 2 for the generator's variants, which carry the BatchNorm prologue AND the
 // effgrad operand (their prefetch registers spill at 168); C = 32 -> 2 (76 KB of LDS)
-template <int C, bool AFF, int RS, bool EFF>
-__host__ __device__ constexpr int b3_occ() { return C == 16 ? ((AFF && EFF) ? 2 : 3) : 2; }
+__host__ __device__ constexpr int b3_occ(int C, bool aff, bool eff) { return C == 16 ? ((aff && eff) ? 2 : 3) : 2; }
 
 template <int C, bool AFF, int RS, bool EFF>
-__global__ __launch_bounds__(256, (b3_occ<C, AFF, RS, EFF>())) void conv3x3_bwd_kernel(Bwd3Args a, int tiles_w, int tpi, int tpb, int bpi, int nblk) {
+__global__ __launch_bounds__(256, b3_occ(C, AFF, EFF)) void conv3x3_bwd_kernel(Bwd3Args a, int tiles_w, int tpi, int tpb, int bpi, int nblk) {
     typedef B3Cfg<C> K;
-    constexpr int NT = K::NT, CH = K::CH, CPP = K::CPP, PS = K::PS, AW = K::AW, KP = K::KP;
+    constexpr int NT = K::NT, CH = K::CH, CPP = K::CPP, PS = K::PS, PSE = K::PSE, AW = K::AW, KP = K::KP;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* wl = smem;                                   // [C][WSB] dgrad pack
     char* gl = smem + K::W_BYTES;                      // [AH*AW][PS] g_eff halo image (later: epilogue buffer / fold scratch)
@@ -101,11 +81,7 @@ __global__ __launch_bounds__(256, (b3_occ<C, AFF, RS, EFF>())) void conv3x3_bwd_
     const int lr = lane & 15, lg = lane >> 4;
     const int H = a.H, W = a.W;
     const int Hs = a.src.Hs, Ws = a.src.Ws;
-    int bid = blockIdx.x;
-    {   // XCD-aware order: blocks b and b + 8 share an XCD (and its L2): every XCD walks one contiguous run of tiles
-        const int q = nblk / 8, r = nblk % 8, xcd = bid % 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
+    const int bid = xcd_block_order(blockIdx.x, nblk);      // every XCD walks one contiguous run of tiles
     const int n = bid / bpi;                           // a block stays inside ONE image (per-image BatchNorm accumulators)
     const int t0 = (bid - n * bpi) * tpb;
     const int t1 = min(t0 + tpb, tpi);
@@ -116,21 +92,8 @@ __global__ __launch_bounds__(256, (b3_occ<C, AFF, RS, EFF>())) void conv3x3_bwd_
         const int row = idx / (KP / 8), kc = idx - row * (KP / 8);
         *(bf16x8*)(wl + row * K::WSB + kc * 16) = *(const bf16x8*)((const bf16*)a.w_bwd + (long)row * KP + kc * 8);
     }
-    if (AFF) {
-        for (int i = tid; i < C; i += 256) {
-            aff_s[i] = a.src.scale[(long)n * a.src.aff_nstride + i];
-            aff_s[C + i] = a.src.shift[(long)n * a.src.aff_nstride + i];
-        }
-    }
-    if (EFF) {
-        const int ev = (a.n_per_event > 0) ? n / a.n_per_event : 0;
-        for (int i = tid; i < C; i += 256) {
-            eff_s[i] = a.dstat[(long)ev * 2 * C + i];
-            eff_s[C + i] = 2.f * a.dstat[(long)ev * 2 * C + C + i];
-        }
-    }
-    typedef const __attribute__((address_space(3))) float* lds_cf;
-    typedef const __attribute__((address_space(3))) f32x4* lds_cf4;
+    if (AFF) stage_bn_rows(aff_s, a.src, n, C);
+    if (EFF) stage_eff_rows(eff_s, a.dstat, n, a.n_per_event, C);
 
     auto tile_coords = [&](int t, int& h0, int& w0) {
         h0 = (t / tiles_w) * B3_TH;
@@ -178,15 +141,7 @@ __global__ __launch_bounds__(256, (b3_occ<C, AFF, RS, EFF>())) void conv3x3_bwd_
             const int hh = h0 - 1 + hp / AW, ww = w0 - 1 + hp % AW;
             bf16x8 o = zero8();
             if (hh >= 0 && hh < H && ww >= 0 && ww < W) {
-                if (EFF) {
-                    const f32x4 d0 = *(lds_cf4)(eff_s + zo + cc * 8), d1 = *(lds_cf4)(eff_s + zo + cc * 8 + 4);
-                    const f32x4 q0 = *(lds_cf4)(eff_s + zo + C + cc * 8), q1 = *(lds_cf4)(eff_s + zo + C + cc * 8 + 4);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i)
-                        o[i] = f2bf(bf2f(rg[j][i]) + (i < 4 ? d0[i & 3] : d1[i & 3]) + bf2f(ry[j][i]) * (i < 4 ? q0[i & 3] : q1[i & 3]));
-                } else {
-                    o = rg[j];
-                }
+                o = EFF ? effgrad8(rg[j], ry[j], eff_s + zo + cc * 8, C) : rg[j];
             }
             *(bf16x8*)(gl + hp * PS + cc * 16) = o;
         }
@@ -268,7 +223,7 @@ __global__ __launch_bounds__(256, (b3_occ<C, AFF, RS, EFF>())) void conv3x3_bwd_
             for (int r = 0; r < B3_TH; ++r) {
                 // (up-sampled source: conv pixel (r, col) reads source pixel (r >> 1, col >> 1) of the compact tile -- every lane of a transposed
                 //  read supplies its own row address, pairs of lanes share one)
-                bf16x8 b = (RS == 0) ? b3_frag_T(xl, PS, r * B3_TW + lg * 4, njw * 16, lr) : b3_frag_T_up(xl, PS, r >> 1, lg * 4, njw * 16, lr);
+                bf16x8 b = (RS == 0) ? tr_frag((const bf16*)xl, PSE, r * B3_TW + lg * 4, 16, njw * 16, lr) : b3_frag_T_up((const bf16*)xl, PSE, r >> 1, lg * 4, njw * 16, lr);
                 if (AFF) {                                  // forward prologue on the fragment: 8 pixels of channel njw*16 + lr
                     const float sc = *(lds_cf)(aff_s + zo + njw * 16 + lr), sh = *(lds_cf)(aff_s + zo + C + njw * 16 + lr);
 #pragma unroll
@@ -280,7 +235,7 @@ __global__ __launch_bounds__(256, (b3_occ<C, AFF, RS, EFF>())) void conv3x3_bwd_
                 for (int j = 0; j < NTAP; ++j) {
                     const int tp = (C == 16) ? min(wave + 4 * j, 8) : j;      // (C = 16, waves 1..3: slot 2 repeats tap 8 and is dropped at the end)
                     const int dy = tp / 3, dx = tp - dy * 3;
-                    const bf16x8 af = b3_frag_T(gl, PS, (r + 2 - dy) * AW + (2 - dx) + lg * 4, mtw * 16, lr);
+                    const bf16x8 af = tr_frag((const bf16*)gl, PSE, (r + 2 - dy) * AW + (2 - dx) + lg * 4, 16, mtw * 16, lr);
                     accw[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, b, accw[j], 0, 0, 0);
                     if (tp == 4 && want_cs && njw == 0 && (C == 32 || j == 1)) accc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, ones, accc, 0, 0, 0);
                 }
@@ -299,8 +254,7 @@ __global__ __launch_bounds__(256, (b3_occ<C, AFF, RS, EFF>())) void conv3x3_bwd_
                     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) wbuf[(m2 * 16 + lg * 4 + r) * K::LDW + nt * 16 + lr] = acc[2 * half + m2][nt][r];
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();
                 constexpr int EIT = 32 * CPP / 64;
 #pragma unroll
                 for (int it = 0; it < EIT; ++it) {
@@ -310,29 +264,13 @@ __global__ __launch_bounds__(256, (b3_occ<C, AFF, RS, EFF>())) void conv3x3_bwd_
                     float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                     const int px = (2 * wave + half) * B3_TW + row;
                     const bf16x8 xv = *(const bf16x8*)(xl + px * PS + ecc * 16);
-                    if (AFF) {
-                        const f32x4 c0 = *(lds_cf4)(aff_s + zo + ecc * 8), c1 = *(lds_cf4)(aff_s + zo + ecc * 8 + 4);
-                        const f32x4 e0 = *(lds_cf4)(aff_s + zo + C + ecc * 8), e1 = *(lds_cf4)(aff_s + zo + C + ecc * 8 + 4);
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            const float xf = bf2f(xv[i]);
-                            const float sc = i < 4 ? c0[i & 3] : c1[i & 3], sh = i < 4 ? e0[i & 3] : e1[i & 3];
-                            const float d = !(xf * sc + sh > 0.f) ? 0.f : v[i];
-                            s1[i] += d;
-                            s2[i] += d * xf;
-                            v[i] = d * sc;
-                        }
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) v[i] = (bf2f(xv[i]) > 0.f) ? v[i] : 0.f;
-                    }
+                    prologue_bwd8<AFF>(v, xv, aff_s + zo + ecc * 8, C, s1, s2);
                     bf16x8 o;
 #pragma unroll
                     for (int i = 0; i < 8; ++i) o[i] = f2bf(v[i]);
                     *(bf16x8*)((bf16*)a.dx + (((long)n * H + h0 + 2 * wave + half) * W + w0 + row) * C + ecc * 8) = o;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();
             }
         } else {
             // up-sampled source: tile rows 2w, 2w+1 are source row w of the 4 x 16 source tile; item = (source pixel j, chunk) per lane
@@ -350,8 +288,7 @@ __global__ __launch_bounds__(256, (b3_occ<C, AFF, RS, EFF>())) void conv3x3_bwd_
                     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) wbuf[(m2 * 16 + lg * 4 + r) * K::LDW + nt * 16 + lr] = acc[2 * half + m2][nt][r];
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();
                 if (act) {
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
@@ -364,27 +301,11 @@ __global__ __launch_bounds__(256, (b3_occ<C, AFF, RS, EFF>())) void conv3x3_bwd_
                         }
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();
             }
             if (act) {
                 const bf16x8 xv = *(const bf16x8*)(xl + (wave * 16 + j) * PS + ecc * 16);
-                if (AFF) {
-                    const f32x4 c0 = *(lds_cf4)(aff_s + zo + ecc * 8), c1 = *(lds_cf4)(aff_s + zo + ecc * 8 + 4);
-                    const f32x4 e0 = *(lds_cf4)(aff_s + zo + C + ecc * 8), e1 = *(lds_cf4)(aff_s + zo + C + ecc * 8 + 4);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const float xf = bf2f(xv[i]);
-                        const float sc = i < 4 ? c0[i & 3] : c1[i & 3], sh = i < 4 ? e0[i & 3] : e1[i & 3];
-                        const float d = !(xf * sc + sh > 0.f) ? 0.f : v[i];
-                        s1[i] += d;
-                        s2[i] += d * xf;
-                        v[i] = d * sc;
-                    }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] = (bf2f(xv[i]) > 0.f) ? v[i] : 0.f;
-                }
+                prologue_bwd8<AFF>(v, xv, aff_s + zo + ecc * 8, C, s1, s2);
                 bf16x8 o;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) o[i] = f2bf(v[i]);
@@ -394,43 +315,8 @@ __global__ __launch_bounds__(256, (b3_occ<C, AFF, RS, EFF>())) void conv3x3_bwd_
         __syncthreads();                                   // transpose buffers / x tile free: the next tile is staged over them
     }
 
-    // ---- block end 1: per-image BatchNorm accumulators (sum d, sum d*x): the lanes that share a chunk are folded through LDS, the four
-    // waves in a fixed order, one add per channel and block into replica slot bid % BNB_REPL of the image
-    if (AFF && a.bn_acc != nullptr) {
-        float* sx = (float*)gl + wave * STATS_SX_FLOATS;
-        constexpr int SH = 64 / CPP;
-#pragma unroll
-        for (int w = 0; w < 2; ++w) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) sx[i * 64 + (lane ^ i)] = w ? s2[i] : s1[i];
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (lane < 8 * CPP) {
-                const int cc = lane % CPP, i = lane / CPP;
-                float tt = 0.f;
-#pragma unroll
-                for (int k = 0; k < SH; ++k) tt += sx[i * 64 + ((cc + CPP * k) ^ i)];
-                red[(wave * C + cc * 8 + i) * 2 + w] = tt;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-        __syncthreads();
-        if (tid < C) {
-            float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < 4; ++wv) {
-                x1 += red[(wv * C + tid) * 2 + 0];
-                x2 += red[(wv * C + tid) * 2 + 1];
-            }
-            // slot = this block's index inside its image when bn_slots == blocks per image (one adder per address: bit-reproducible)
-            const int R = a.bn_slots > 0 ? a.bn_slots : BNB_REPL;
-            float* st = a.bn_acc + ((long)n * R + bid % R) * 2 * C;
-            atomicAdd(st + tid, x1);
-            atomicAdd(st + C + tid, x2);
-        }
-        __syncthreads();
-    }
+    // ---- block end 1: per-image BatchNorm accumulators (sum d, sum d*x), folded through the halo image's LDS
+    if (AFF && a.bn_acc != nullptr) bn_acc_flush<C>(s1, s2, red, (float*)gl, a.bn_acc, a.bn_slots, n, bid);
     // ---- block end 2: dW slab [C][KP] (+ column sums): every wave owns disjoint entries (C = 32: its (cout tile, cin tile) pair; C = 16: its
     // taps), so the slab is bit-reproducible (no LDS float atomics)
     {
@@ -471,63 +357,40 @@ static bool b3_shape_ok(int C, int rs, bool aff, bool relu) { return (C == 16 ||
 // generator's (BatchNorm prologue + effgrad).
 static bool b3_variant_ok(int C, int rs, bool aff, bool eff) { return aff == eff && !(C == 32 && rs == 0 && aff && eff); }
 
-static int b3_plan(const Bwd3Args& a, B3Plan& p) {
+// query: a workspace / slots query, made before the slab workspace exists
+static int b3_plan(const Bwd3Args& a, B3Plan& p, bool query = false) {
     CHECK_ARG(b3_shape_ok(a.C, a.src.rs, a.src.scale != nullptr, a.src.relu != 0), "conv3x3_bwd: C = %d, rs %d, relu %d is not instantiated", a.C, a.src.rs, a.src.relu);
     CHECK_ARG(b3_variant_ok(a.C, a.src.rs, a.src.scale != nullptr, a.y != nullptr), "conv3x3_bwd: this (C, rs, affine prologue, effgrad) combination is not instantiated");
     CHECK_ARG(a.H % B3_TH == 0 && a.W % B3_TW == 0, "conv3x3_bwd: H %% 8 == 0 and W %% 32 == 0 required (%d x %d)", a.H, a.W);
     if (a.src.rs == 0) CHECK_ARG(a.H == a.src.Hs && a.W == a.src.Ws, "conv3x3_bwd: geometry mismatch");
     if (a.src.rs == 1) CHECK_ARG(a.H == 2 * a.src.Hs && a.W == 2 * a.src.Ws, "conv3x3_bwd: upsample geometry mismatch");
     CHECK_ARG(a.Kpad == ((9 * a.C + 31) / 32) * 32, "conv3x3_bwd: Kpad must be the canonical pack row length");
-    CHECK_ARG(a.Cg >= a.C && a.Cg % 8 == 0 && a.src.Cx >= a.C && a.src.Cx % 8 == 0, "conv3x3_bwd: bad channel strides");
-    CHECK_ARG((a.src.scale == nullptr) == (a.src.shift == nullptr), "conv3x3_bwd: scale / shift must come together");
-    CHECK_ARG((a.y == nullptr) == (a.dstat == nullptr), "conv3x3_bwd: the effgrad operands y / dstat must come together");
-    CHECK_ARG(a.n_per_event >= 0 && (a.n_per_event == 0 || a.N % a.n_per_event == 0), "conv3x3_bwd: N is not a whole number of events");
+    const int crc = bwd_common_checks("conv3x3_bwd", a.src, a.y, a.dstat, a.N, a.n_per_event, a.Cg, a.C, a.C);
+    if (crc != 0) return crc;
     CHECK_ARG((a.src.scale != nullptr) == (a.bn_acc != nullptr), "conv3x3_bwd: the affine prologue and bn_acc come together");
-    CHECK_ARG(a.dx != nullptr && a.dw != nullptr && a.partials != nullptr, "conv3x3_bwd: dx, dw and the slab workspace are required");
+    CHECK_ARG(a.dx != nullptr && a.dw != nullptr && (query || a.partials != nullptr), "conv3x3_bwd: dx, dw and the slab workspace are required");
     CHECK_ARG((a.flags & ~IEAGAN_BWD_NO_REDUCE) == 0 && a.bn_slots >= 0, "conv3x3_bwd: unknown flag bits 0x%x / bad bn_slots %d", a.flags, a.bn_slots);
     p.tiles_w = a.W / B3_TW;
     p.tpi = p.tiles_w * (a.H / B3_TH);
-    // ONE round of persistent blocks: whole blocks per image
-    const int occ = a.C == 16 ? ((a.src.scale != nullptr && a.y != nullptr) ? 2 : 3) : 2;      // == b3_occ of the variant
-    const int slots = 256 * occ;
-    int bpi = slots / a.N;
-    if (bpi < 1) bpi = 1;
-    int tpb = (p.tpi + bpi - 1) / bpi;
-    if (tpb < 2 && p.tpi >= 2) tpb = 2;
-    bpi = (p.tpi + tpb - 1) / tpb;
-    p.tpb = tpb;
-    p.bpi = bpi;
-    p.nblk = bpi * a.N;
-    const int PS = a.C == 16 ? 32 : 96;
+    const PersistentPlan pp = persistent_plan(p.tpi, a.N, b3_occ(a.C, a.src.scale != nullptr, a.y != nullptr), p.tpi >= 2 ? 2 : 1, 1);
+    p.tpb = pp.tpb;
+    p.bpi = pp.bpi;
+    p.nblk = pp.nblk;
+    const int PS = 2 * lds_stride_odd32(a.C);
     const int KP = a.Kpad;
     p.lds = (size_t)a.C * (KP * 2 + 16) + (size_t)(B3_TH + 2) * (B3_TW + 2) * PS + (a.src.rs == 1 ? (size_t)64 * PS : (size_t)B3_TH * B3_TW * PS);
     p.ws_elems = (long)p.nblk * a.C * KP;
     return 0;
 }
 
-extern "C" long ieagan_conv3x3_bwd_workspace(const ieagan_conv3x3_bwd_desc* d) {
-    B3Plan p;
-    if (d == nullptr) return 0;
-    Bwd3Args a = *d;
-    if (a.partials == nullptr) a.partials = (float*)16;      // (the query is made before the workspace exists)
-    if (b3_plan(a, p) != 0) return 0;
-    return p.ws_elems;
-}
-
-extern "C" int ieagan_conv3x3_bwd_slots(const ieagan_conv3x3_bwd_desc* d) {
-    B3Plan p;
-    if (d == nullptr) return IEAGAN_EINVAL;
-    Bwd3Args a = *d;
-    if (a.partials == nullptr) a.partials = (float*)16;      // (the query is made before the workspace exists)
-    const int rc = b3_plan(a, p);
-    return rc != 0 ? rc : p.bpi;
-}
+// (the queries are made before the slab workspace exists)
+static int b3_plan_query(const Bwd3Args& a, B3Plan& p) { return b3_plan(a, p, true); }
+extern "C" long ieagan_conv3x3_bwd_workspace(const ieagan_conv3x3_bwd_desc* d) { return bwd_plan_query<B3Plan>(d, b3_plan_query, false); }
+extern "C" int ieagan_conv3x3_bwd_slots(const ieagan_conv3x3_bwd_desc* d) { return (int)bwd_plan_query<B3Plan>(d, b3_plan_query, true); }
 
 extern "C" int ieagan_conv3x3_bwd_supported(int C, int rs, int affine, int relu, int eff, int H, int W) {
     return (b3_shape_ok(C, rs, affine != 0, relu != 0) && b3_variant_ok(C, rs, affine != 0, eff != 0) && H % B3_TH == 0 && W % B3_TW == 0) ? 1 : 0;
 }
-
-int wgrad_reduce_launch(const float* part, float* dw, int S, int Cout, int Kpad, int K, hipStream_t st);      // conv_wgrad.hip
 
 template <int C, bool AFF, int RS, bool EFF>
 static int b3_go(const Bwd3Args& a, const B3Plan& p, hipStream_t st) {

@@ -18,11 +18,7 @@ struct TileRun {
 };
 __device__ __forceinline__ TileRun tile_run(int nblk, int gy, int bpe, int tpe, int tpb) {
     TileRun r;
-    int bid = blockIdx.x;
-    {
-        const int tot = nblk * gy, q = tot / 8, rem = tot % 8, xcd = bid % 8;
-        bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + bid / 8;
-    }
+    const int bid = xcd_block_order(blockIdx.x, nblk * gy);
     r.column = bid % gy;
     r.bid = bid / gy;
     r.event = r.bid / bpe;

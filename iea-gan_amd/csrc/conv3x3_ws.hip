@@ -71,12 +71,10 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 4 ? 4 : 3)) void conv3x3_ws
             int n, h0, w0;
             tile_coords(t, n, h0, w0);
             if (AFF && n != aff_n) {       // this wave's private copy of image n's scale / shift rows (wave-ordered LDS: no block barrier)
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();
                 const int c = lane & 31;
                 if (c < CIN) aff_w[lane] = (lane < 32 ? a.src.scale : a.src.shift)[(long)n * a.src.aff_nstride + c];
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();
                 aff_n = n;
             }
 #pragma unroll

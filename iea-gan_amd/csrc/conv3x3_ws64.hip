@@ -83,12 +83,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_ws64_kernel(ConvArgs a, int ti
             int n, h0, w0;
             tile_coords(t, n, h0, w0);
             if (AFF && n != aff_n) {       // this wave's private copy of image n's scale / shift rows (wave-ordered LDS: no block barrier)
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();
                 aff_w[lane] = a.src.scale[(long)n * a.src.aff_nstride + lane];
                 aff_w[CIN + lane] = a.src.shift[(long)n * a.src.aff_nstride + lane];
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();
                 aff_n = n;
             }
 #pragma unroll
@@ -138,12 +136,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_ws64_kernel(ConvArgs a, int ti
             int n, h0, w0;
             tile_coords(t, n, h0, w0);
             if (BNB && n != bnb_n) {       // this wave's private copy of image n's BatchNorm-backward rows (a BNB launch has no prologue rows)
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();
                 aff_w[lane] = a.bnb_scale[(long)n * a.bnb_nstride + lane];
                 aff_w[CIN + lane] = a.bnb_shift[(long)n * a.bnb_nstride + lane];
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_fence();
                 bnb_n = n;
             }
             const tile_pix<1, FULL> pix(n, h0, w0, 2 * wl, H, W);       // one m-tile of each of consumer wl's two tile rows

@@ -13,6 +13,7 @@ typedef ieagan_wgrad_desc WgradArgs;
 
 int conv_gather_launch(const ConvArgs& a, hipStream_t st);
 int conv_wgrad_launch(const WgradArgs& a, hipStream_t st, int use_tr);
+int wgrad_reduce_launch(const float* part, float* dw, int S, int Cout, int Kpad, int K, hipStream_t st);      // conv_wgrad.hip: dw += sum of S slabs
 int conv3x3_lds_launch(const ConvArgs& a, hipStream_t st);       // 1 = launched, 0 = not applicable (caller falls back to conv3x3_halo), < 0 = error
 int conv3x3_ws64_launch(const ConvArgs& a, hipStream_t st);       // 1 = launched, 0 = not applicable (caller goes on to conv3x3_lds), < 0 = error
 int conv3x3_ws_launch(const ConvArgs& a, hipStream_t st);         // 1 = launched, 0 = not applicable (caller falls back to conv3x3_halo)

@@ -155,8 +155,7 @@ __global__ __launch_bounds__(256) void conv_1toC_kernel(const float* __restrict_
             for (int r = 0; r < 4; ++r) o[(4 * lg + r) * LDO + nt * 16 + lr] = d[r];      // D[pixel 4lg+r][cout lr]
         }
         // wave-private buffer: LDS operations of one wave complete in order, the fences keep the compiler from moving them
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_fence();
 #pragma unroll
         for (int it = 0; it < (16 * (C / 8) + 63) / 64; ++it) {
             const int item = it * 64 + lane;
@@ -183,8 +182,7 @@ __global__ __launch_bounds__(256) void conv_1toC_kernel(const float* __restrict_
                 *(bf16x8*)(out + (((size_t)n * H + y) * W + x) * C + cc * 8) = ov;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // the next m-tile overwrites the buffer
-        __builtin_amdgcn_wave_barrier();
+        wave_fence();      // the next m-tile overwrites the buffer
     }
     }
     if (BNB && bn_n >= 0) bnb_flush(bn_n);
@@ -403,17 +401,6 @@ extern "C" int ieagan_conv_Cto1(const void* x, const float* scale, const float* 
 // ------------------------------------------------------------------------------------------------
 #define W1_TH 8
 #define W1_TW 32
-__device__ __forceinline__ bf16x8 tr8(const bf16* lds, int stride_elems, int pix0, int col0, int lr) {
-    const int q = lr >> 2, p = lr & 3;
-    const bf16* p0 = lds + (pix0 + q) * stride_elems + col0 + 4 * p;
-    const bf16* p1 = p0 + 4 * stride_elems;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p0);
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p1);
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
 
 template <int C, bool AFF, bool RELU>
 __global__ __launch_bounds__(256) void wgrad_c1_kernel(const float* __restrict__ img, const float* __restrict__ tanh_y,
@@ -500,7 +487,7 @@ __global__ __launch_bounds__(256) void wgrad_c1_kernel(const float* __restrict__
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                const bf16x8 b = tr8(tl, C, row * W1_TW + 8 * lg, nt * 16, lr);
+                const bf16x8 b = tr_frag(tl, C, row * W1_TW + 8 * lg, 4, nt * 16, lr);
                 acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, b, acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, b, acc[nt], 0, 0, 0);
             }

@@ -59,8 +59,7 @@ __device__ __forceinline__ void stats_fold(float (&s1)[8], float (&s2)[8], float
     for (int w = 0; w < 2; ++w) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) sx[i * 64 + (lane ^ i)] = w ? s2[i] : s1[i];
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // make the wave's stores visible to its other lanes
-        __builtin_amdgcn_wave_barrier();
+        wave_fence();      // make the wave's stores visible to its other lanes
         if (lane < 8 * CPP) {                         // output (chunk cc, channel i of the chunk): 8 * CPP <= 64 per wave
             const int cc = lane % CPP, i = lane / CPP;
             float t = 0.f;
@@ -68,8 +67,7 @@ __device__ __forceinline__ void stats_fold(float (&s1)[8], float (&s2)[8], float
             for (int k = 0; k < SH; ++k) t += sx[i * 64 + ((cc + CPP * k) ^ i)];
             red[(wave * NT * 16 + cc * 8 + i) * 2 + w] = t;
         }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // phase 1 overwrites what other lanes of this wave just read
-        __builtin_amdgcn_wave_barrier();
+        wave_fence();      // phase 1 overwrites what other lanes of this wave just read
     }
 }
 
@@ -149,8 +147,7 @@ __device__ __forceinline__ void conv_epilogue_put(const f32x4 (&acc)[MTS][NT], f
             for (int r = 0; r < 4; ++r) wlds[(mt * 16 + lg * 4 + r) * LDW + nt * 16 + lr] = acc[mt][nt][r];
     // the transpose buffer is private to this wave: its LDS operations complete in order, the fence only pins the compiler
     // (a block-wide barrier here made every wave wait for the slowest one four times per tile)
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_fence();
 }
 
 template <bool BNBOK, int NT, int MTS = 2, bool EARLY = true, typename PixFn>
@@ -288,8 +285,8 @@ __device__ __forceinline__ void conv_epilogue_finish(const ConvArgs& a, const fl
         }
         *(bf16x8*)((bf16*)a.out + m * a.Cout + co0) = o;
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // the caller may overwrite the buffer (next half / next phase);
-    __builtin_amdgcn_wave_barrier();                             // anything that touches ANOTHER wave's region needs a block barrier
+    wave_fence();      // the caller may overwrite the buffer (next half / next phase); anything that touches ANOTHER wave's region needs a
+                       // block barrier
 }
 
 template <bool BNBOK, int NT, int MTS = 2, bool EARLY = true, typename PixFn>

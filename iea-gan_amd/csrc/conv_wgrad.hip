@@ -13,32 +13,18 @@
 
 // K(pixel)-major fragment of one column block from a [pixel rows][channels] 16-bit LDS image: 8 values = rows pix0 .. pix0+3 and
 // pix0+hi .. pix0+hi+3 of column (col0 + lr).
-// TR: two ds_read_b64_tr_b16 (lane 4q+p of a 16-lane group supplies row q, columns 4p..4p+3 and receives column (lane&15) of
-// the 4 rows).  !TR: eight scalar reads (reference path for the test).
-// Bank layout: one half-wave instruction (lane groups lg = 0, 1) reads 8 image rows x 32 bytes.  The callers assign the rows so
-// that these are 8 CONSECUTIVE rows (lg 0 -> rows +0..3 / +8..11, lg 1 -> rows +4..7 / +12..15) and pad the row stride to an odd
-// multiple of 32 bytes (wg_stride): 8 consecutive rows then cover the 64 banks exactly once.  (With the natural strides the same
-// reads were 2-way (C = 16 / 32), 4-way (C = 64) and 8-way (C = 128) bank conflicts.)
+// TR: tr_frag (common.h).  !TR: eight scalar reads (reference path for the test).
+// Bank layout: the callers assign the rows so that one half-wave instruction (lane groups lg = 0, 1) reads 8 CONSECUTIVE rows
+// (lg 0 -> rows +0..3 / +8..11, lg 1 -> rows +4..7 / +12..15) and pad the row stride with lds_stride_odd32.  (With the natural
+// strides the same reads were 2-way (C = 16 / 32), 4-way (C = 64) and 8-way (C = 128) bank conflicts.)
 template <bool TR>
 __device__ __forceinline__ bf16x8 frag_T(const bf16* lds, int stride_elems, int pix0, int hi, int col0, int lr) {
+    if (TR) return tr_frag(lds, stride_elems, pix0, hi, col0, lr);
     bf16x8 f;
-    if (TR) {
-        const int q = lr >> 2, p = lr & 3;
-        const bf16* p0 = lds + (pix0 + q) * stride_elems + col0 + 4 * p;
-        const bf16* p1 = p0 + hi * stride_elems;
-        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p0);
-        const bf16x4 hh = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p1);
-        f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-        f[4] = hh[0]; f[5] = hh[1]; f[6] = hh[2]; f[7] = hh[3];
-    } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = lds[(pix0 + (j < 4 ? j : hi + j - 4)) * stride_elems + col0 + lr];
-    }
+    for (int j = 0; j < 8; ++j) f[j] = lds[(pix0 + (j < 4 ? j : hi + j - 4)) * stride_elems + col0 + lr];
     return f;
 }
-
-// row stride (elements) of a C-channel LDS image: an odd multiple of 32 bytes
-__host__ __device__ constexpr int wg_stride(int C) { return ((C / 16) % 2 == 0) ? C + 16 : C; }
 
 // Block = 4 waves: MT m-tiles (16 couts each) x 4*NJ n-tile slots ((tap, 16 cins) pairs, dealt round-robin to the waves) over
 // `tiles_per_block` pixel tiles of 8 x 16; fp32 atomics into dW at the end (split-K over the blocks).
@@ -56,14 +42,14 @@ __global__ __launch_bounds__(256, (CINV > 0 ? (CINV == 16 ? 4 : (CINV == 32 ? 3 
     constexpr int GC = MT * 16;                   // cout columns of the g tile
     constexpr int GCH = (WG_TH * WG_TW * (GC / 8) + 255) / 256;                     // g chunks per thread
     constexpr int ACH = PFW ? (AH * AW * (CINV / 8) + 255) / 256 : 1;               // a chunks per thread
-    const int GS = a.pad_rows ? wg_stride(GC) : GC;      // padded row strides (elements): see frag_T
+    const int GS = a.pad_rows ? lds_stride_odd32(GC) : GC;      // padded row strides (elements): see frag_T
     bf16* lds_g = (bf16*)smem;                    // [WG_TH*WG_TW][GS]
     bf16* lds_a = lds_g + WG_TH * WG_TW * GS;     // [AH*AW][AS]
     __shared__ __attribute__((aligned(32))) float aff_s[(AFF && PFW) ? 2 * AFF_MAXC : 8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 15, lg = lane >> 4;
     const int H = a.H, W = a.W, Cin = (CINV > 0) ? CINV : a.Cin;
-    const int AS = a.pad_rows ? wg_stride(Cin) : Cin;
+    const int AS = a.pad_rows ? lds_stride_odd32(Cin) : Cin;
     const int tiles_w = (W + WG_TW - 1) / WG_TW, tiles_h = (H + WG_TH - 1) / WG_TH;
     const int tiles_img = tiles_w * tiles_h;
     const long tiles_total = (long)a.N * tiles_img;
@@ -561,7 +547,7 @@ static int wgrad_plan(const WgradArgs& a, int use_tr, WgradPlan& p) {
     p.tpb = tpb;
     p.gx = (int)((tiles + tpb - 1) / tpb);
     const int halo = (a.taps == 9) ? 1 : 0;
-    size_t lds = (size_t)WG_TH * WG_TW * wg_stride(mt * 16) * 2 + (size_t)(WG_TH + 2 * halo) * (WG_TW + 2 * halo) * wg_stride(a.Cin) * 2;
+    size_t lds = (size_t)WG_TH * WG_TW * lds_stride_odd32(mt * 16) * 2 + (size_t)(WG_TH + 2 * halo) * (WG_TW + 2 * halo) * lds_stride_odd32(a.Cin) * 2;
     p.pad_rows = lds <= 160 * 1024;              // conflict-free padded LDS rows unless the tiles then exceed the 160 KB of a CU
     if (!p.pad_rows) lds = (size_t)WG_TH * WG_TW * mt * 16 * 2 + (size_t)(WG_TH + 2 * halo) * (WG_TW + 2 * halo) * a.Cin * 2;
     CHECK_ARG(lds <= 160 * 1024, "wgrad: LDS request %zu too large", lds);

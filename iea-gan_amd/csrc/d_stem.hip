@@ -50,23 +50,6 @@ struct DStemArgs {
     float* dimg;          // fp32 [N, H, W]      (d_stem_dimg)
 };
 
-// K(pixel)-major fragment: 8 consecutive rows pix0 .. pix0+7 of column (col0 + lr) of a [pixel][channel] 16-bit LDS image
-__device__ __forceinline__ bf16x8 st_tr8(const bf16* lds, int stride_elems, int pix0, int col0, int lr) {
-    const int q = lr >> 2, p = lr & 3;
-    const bf16* p0 = lds + (pix0 + q) * stride_elems + col0 + 4 * p;
-    const bf16* p1 = p0 + 4 * stride_elems;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p0);
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)p1);
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
-
-#define ST_WAVE_FENCE()                                     \
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); \
-    __builtin_amdgcn_wave_barrier()
-
 #define ST_HW (ST_TW + 4)  // row stride of the halo image (words)
 #define ST_HN ((((ST_TH + 2) * (ST_TW + 2)) + 255) / 256)                  // halo values per thread
 // The image halo in LDS: one word per element, bf16(v) in the lower and bf16(v - bf16(v)) in the upper half.  Two words make one dword
@@ -156,7 +139,7 @@ __device__ __forceinline__ void st_h0_tile(const StHalo* halo, int wave, int lan
             }
         }
     }
-    ST_WAVE_FENCE();
+    wave_fence();
 }
 
 // Two accumulator tiles A, B with a lane's four bf16 values each (rows 4 lg .. 4 lg + 3 of column lr) -> 16 bytes per lane: lane group
@@ -260,7 +243,7 @@ __global__ __launch_bounds__(256, 4) void d_stem_fwd_kernel(DStemArgs a, int til
             *(bf16x8*)(p0s + ppx * ST_XS + cc4 * 8) = pv;
             *(bf16x8*)((bf16*)a.p0 + (((long)t.n * Hp + yp) * Wp + (t.x0 >> 1) + ppx) * ST_C0 + cc4 * 8) = pv;
         }
-        ST_WAVE_FENCE();
+        wave_fence();
         // ---- conv_sc: sc[ppx][32] = p0[ppx][32] Wsc^T + bsc, D[cout nt*16 + 4 lg + r][pooled pixel lr]
         {
             const bf16x8 pf = *(const bf16x8*)(p0s + lr * ST_XS + lg * 8);
@@ -383,15 +366,15 @@ __global__ __launch_bounds__(256, 2) void d_stem_bwd_kernel(DStemArgs a, int til
                 }
             }
         }
-        ST_WAVE_FENCE();
+        wave_fence();
         // ---- weight gradients: K = the 64 pixels of the wave's two rows, 8 consecutive pixels of a row per lane group
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
             const int pix0 = rr * 32 + 8 * lg;
             // dW1[cout lr][cin] += dh1^T h0;  db1 via an all-ones B tile
-            const bf16x8 ag = st_tr8(g1s, ST_C1, pix0, 0, lr);
+            const bf16x8 ag = tr_frag(g1s, ST_C1, pix0, 4, 0, lr);
 #pragma unroll
-            for (int nj = 0; nj < 2; ++nj) aw1[nj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ag, st_tr8(h0s, ST_XS, pix0, nj * 16, lr), aw1[nj], 0, 0, 0);
+            for (int nj = 0; nj < 2; ++nj) aw1[nj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ag, tr_frag(h0s, ST_XS, pix0, 4, nj * 16, lr), aw1[nj], 0, 0, 0);
             ab1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ag, ones, ab1, 0, 0, 0);
             // dW_in[tap lr][c] += patch^T dh0 (image values as bf16 high + low parts, the split done at staging); row 9 = ones -> db_in
             const int row = 2 * wave + rr + wdy;
@@ -403,7 +386,7 @@ __global__ __launch_bounds__(256, 2) void d_stem_bwd_kernel(DStemArgs a, int til
             }
 #pragma unroll
             for (int nj = 0; nj < 2; ++nj) {
-                const bf16x8 b = st_tr8(d0s, ST_XS, pix0, nj * 16, lr);
+                const bf16x8 b = tr_frag(d0s, ST_XS, pix0, 4, nj * 16, lr);
                 awin[nj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, b, awin[nj], 0, 0, 0);
                 awin[nj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, b, awin[nj], 0, 0, 0);
             }

@@ -149,11 +149,9 @@ typedef struct {
     float* dw;                /* fp32 [Cout][Kpad], accumulated; NULL: no weight gradient                            */
     float* partials;          /* optional workspace of ieagan_conv1x1_bwd_workspace(d) floats (two-stage accumulation) */
     float* colsum;            /* optional fp32 [32][Cout] caller-zeroed replicas (bias gradient)                     */
-    int flags;                /* IEAGAN_B1_* (benchmarks: force the 2 / 3 blocks-per-CU build of the kernel)         */
+    int flags;                /* IEAGAN_B1_TP32 (benchmarks) | IEAGAN_BWD_NO_REDUCE; every other bit is refused      */
     int bn_slots;             /* bn_acc is [N][bn_slots][2][Cin]; == ieagan_conv1x1_bwd_slots(d): one adder per slot (bit-reproducible); 0: 8 */
 } ieagan_conv1x1_bwd_desc;
-#define IEAGAN_B1_OCC2 1
-#define IEAGAN_B1_OCC3 2
 #define IEAGAN_B1_TP32 4          /* 32-pixel wave tiles everywhere */
 #define IEAGAN_BWD_NO_REDUCE 16   /* ieagan_conv1x1_bwd / ieagan_conv3x3_bwd: leave the partial dW slabs in `partials` -- the caller folds them with
                                    * ieagan_wgrad_reduce (e.g. on a side stream: nothing in a backward pass reads dW before its end) */

@@ -893,6 +893,9 @@ def test_split_k_gather_matches_plain_gather(dev, taps, Cin, Cout, Hh, Ww, N, ev
     ("d0", 32, 64, True, 64, 64, 3),      # ... as the very first block (no pre-activation)
     ("d", 64, 64, False, 32, 64, 3),      # D s0.1: conv1 64->16, conv4 16->64, identity shortcut
     ("d", 64, 128, True, 64, 64, 2),      # D s1.0: conv1 64->32 fused; conv4 32->128 / conv_sc 64->64 stay on the separate launches
+    ("d", 64, 64, False, 12, 32, 3),      # W % 64 != 0: 32-pixel wave tiles, the last block of an image holds 4 of its 8 tiles; 6 blocks (< 8 XCDs)
+    ("d", 32, 64, True, 24, 64, 3),       # conv1: 9 blocks (9 % 8 == 1); conv4 / conv_sc on the pooled 12x32 source, half-filled last block
+    ("g", 64, 32, True, 8, 32, 4),        # one block per image; conv1 sits exactly at the 1024-pixel threshold set below
 ])
 def test_fused_1x1_backward_matches_separate_launches(dev, ref_cfg, kind, cin, cout, flag, Hh, Ww, N):
     """ieagan_conv1x1_bwd (effgrad + dgrad + prologue backward + wgrad + bias sums in one launch, shortcut gradients added in the
@@ -969,6 +972,10 @@ def test_fused_1x1_backward_matches_separate_launches(dev, ref_cfg, kind, cin, c
     (32, 64, 192, True, 1, True, 4, 2),         # G b9 conv2 with two events of two images (per-event effgrad rows, per-image BatchNorm rows)
     (16, 64, 64, False, 0, False, 40, 1),       # the 64x64 plumbing geometry: one tile row of two tiles per block
     (32, 72, 96, False, 0, False, 5, 1),        # tile counts that do not divide the persistent grid evenly
+    (16, 16, 64, False, 0, False, 3, 1),        # 6 blocks of 2 tiles (fewer blocks than XCDs)
+    (16, 8, 32, True, 1, True, 3, 1),           # up-sampled source, BatchNorm prologue + effgrad, 6 blocks
+    (32, 8, 32, False, 0, False, 5, 1),         # one tile per image: a block never requests a next tile
+    (32, 8, 32, True, 1, True, 4, 2),           # two events, 8 blocks
 ])
 def test_fused_3x3_backward_matches_separate_launches(dev, C, Hs, Ws, aff, rs, stats, N, events):
     """ieagan_conv3x3_bwd (effgrad on load + dgrad with the prologue backward in its store phase + wgrad + bias sums in one launch) against

@@ -481,3 +481,109 @@ def test_weight_gradient_pixel_splits_follow_the_traffic_rule():
         else:
             seen_slabs += 1
     assert seen_direct >= 2 and seen_slabs >= 4, (seen_direct, seen_slabs)
+
+
+def _fused_backward_plan_cases():
+    """(key, entry-point stem, descriptor) of the plan table below.  Pointers are placeholders: the queries never touch memory."""
+    import _hip
+    P = 16
+
+    def b1(N, cin, cout, h, w, rs=0, aff=0, eff=0, flags=0):
+        hs, ws = (2 * h, 2 * w) if rs == 2 else (h, w)
+        src = _hip.SrcDesc(P, cin, hs, ws, rs, P if aff else None, P if aff else None, cin if aff else 0, 1)
+        k = lambda c: ((c + 31) // 32) * 32
+        d = _hip.Conv1x1BwdDesc(N, h, w, cin, cout, k(cin), k(cout), src, P, cout, P if eff else None, P if eff else None, N, None, P, None, 0, 0, 0,
+                                P, 1 if rs == 2 and cin != 16 else 0, P if aff else None, P, None, None, flags, 0)
+        return (f"1x1 {cin}->{cout} N{N} {h}x{w} rs{rs} a{aff} e{eff} f{flags}", "ieagan_conv1x1_bwd", d)
+
+    def b3(N, C, h, w, rs=0, aff=0, npe=0):
+        hs, ws = (h // 2, w // 2) if rs == 1 else (h, w)
+        src = _hip.SrcDesc(P, C, hs, ws, rs, P if aff else None, P if aff else None, C if aff else 0, 1)
+        d = _hip.Conv3x3BwdDesc(N, h, w, C, ((9 * C + 31) // 32) * 32, src, P, C, P if aff else None, P if aff else None, npe or N, P, P,
+                                P if aff else None, P, None, None, 0, 0)
+        return (f"3x3 C{C} N{N} {h}x{w} rs{rs} a{aff} npe{npe}", "ieagan_conv3x3_bwd", d)
+
+    return [
+        # the train step (N = 40): the rows of tools/bwd1x1_bench.py, the same pairs on the 64x192 maps, one 32-pixel-tile form
+        b1(40, 32, 16, 256, 768), b1(40, 16, 64, 128, 384, rs=2), b1(40, 32, 32, 128, 384, rs=2), b1(40, 64, 16, 128, 384),
+        b1(40, 16, 64, 128, 384), b1(40, 64, 32, 128, 384), b1(40, 64, 16, 128, 384, aff=1, eff=1), b1(40, 16, 32, 256, 768, aff=1, eff=1),
+        b1(40, 16, 64, 128, 384, aff=1, eff=1), b1(40, 32, 64, 128, 384, aff=1, eff=1), b1(40, 64, 32, 64, 192), b1(40, 32, 64, 64, 192, aff=1, eff=1),
+        b1(40, 16, 64, 64, 192, rs=2), b1(40, 32, 16, 256, 768, flags=4),
+        # tools/bwd3x3_bench.py: C = 16 / 32 at 256x768 and 128x384
+        b3(40, 16, 256, 768), b3(40, 16, 256, 768, aff=1), b3(40, 16, 256, 768, rs=1, aff=1), b3(40, 16, 128, 384), b3(40, 32, 128, 384),
+        b3(40, 32, 128, 384, rs=1, aff=1), b3(40, 32, 256, 768, rs=1, aff=1),
+        # the edge shapes of test_fused_1x1_backward_matches_separate_launches / test_fused_3x3_backward_matches_separate_launches
+        b1(3, 64, 16, 12, 32), b1(3, 16, 64, 12, 32), b1(3, 32, 16, 24, 64), b1(3, 16, 64, 12, 32, rs=2), b1(3, 32, 32, 12, 32, rs=2),
+        b1(4, 64, 16, 8, 32, aff=1, eff=1), b1(4, 16, 32, 16, 64, aff=1, eff=1),
+        b3(3, 16, 16, 64), b3(3, 16, 16, 64, rs=1, aff=1), b3(5, 32, 8, 32), b3(4, 32, 16, 64, rs=1, aff=1, npe=2),
+        # more images than resident slots, and a shape the kernel does not offer
+        b1(1100, 64, 32, 32, 64), b3(800, 16, 8, 32), b3(40, 32, 128, 384, aff=1),
+    ]
+
+
+# key -> (blocks per image, workspace floats), recorded from the library of the commit before the shared plan (persistent_plan, conv_bwd.h)
+FUSED_BACKWARD_PLANS = {
+    "1x1 32->16 N40 256x768 rs0 a0 e0 f0": (12, 0),
+    "1x1 16->64 N40 128x384 rs2 a0 e0 f0": (12, 0),
+    "1x1 32->32 N40 128x384 rs2 a0 e0 f0": (12, 0),
+    "1x1 64->16 N40 128x384 rs0 a0 e0 f0": (12, 0),
+    "1x1 16->64 N40 128x384 rs0 a0 e0 f0": (12, 0),
+    "1x1 64->32 N40 128x384 rs0 a0 e0 f0": (12, 0),
+    "1x1 64->16 N40 128x384 rs0 a1 e1 f0": (12, 0),
+    "1x1 16->32 N40 256x768 rs0 a1 e1 f0": (12, 0),
+    "1x1 16->64 N40 128x384 rs0 a1 e1 f0": (12, 0),
+    "1x1 32->64 N40 128x384 rs0 a1 e1 f0": (12, 0),
+    "1x1 64->32 N40 64x192 rs0 a0 e0 f0": (12, 0),
+    "1x1 32->64 N40 64x192 rs0 a1 e1 f0": (12, 0),
+    "1x1 16->64 N40 64x192 rs2 a0 e0 f0": (12, 0),
+    "1x1 32->16 N40 256x768 rs0 a0 e0 f4": (12, 0),
+    "3x3 C16 N40 256x768 rs0 a0 npe0": (19, 1945600),
+    "3x3 C16 N40 256x768 rs0 a1 npe0": (12, 1228800),
+    "3x3 C16 N40 256x768 rs1 a1 npe0": (12, 1228800),
+    "3x3 C16 N40 128x384 rs0 a0 npe0": (18, 1843200),
+    "3x3 C32 N40 128x384 rs0 a0 npe0": (12, 4423680),
+    "3x3 C32 N40 128x384 rs1 a1 npe0": (12, 4423680),
+    "3x3 C32 N40 256x768 rs1 a1 npe0": (12, 4423680),
+    "1x1 64->16 N3 12x32 rs0 a0 e0 f0": (2, 0),
+    "1x1 16->64 N3 12x32 rs0 a0 e0 f0": (2, 0),
+    "1x1 32->16 N3 24x64 rs0 a0 e0 f0": (3, 0),
+    "1x1 16->64 N3 12x32 rs2 a0 e0 f0": (2, 0),
+    "1x1 32->32 N3 12x32 rs2 a0 e0 f0": (2, 0),
+    "1x1 64->16 N4 8x32 rs0 a1 e1 f0": (1, 0),
+    "1x1 16->32 N4 16x64 rs0 a1 e1 f0": (2, 0),
+    "3x3 C16 N3 16x64 rs0 a0 npe0": (2, 15360),
+    "3x3 C16 N3 16x64 rs1 a1 npe0": (2, 15360),
+    "3x3 C32 N5 8x32 rs0 a0 npe0": (1, 46080),
+    "3x3 C32 N4 16x64 rs1 a1 npe2": (2, 73728),
+    "1x1 64->32 N1100 32x64 rs0 a0 e0 f0": (1, 2252800),
+    "3x3 C16 N800 8x32 rs0 a0 npe0": (1, 2048000),
+    "3x3 C32 N40 128x384 rs0 a1 npe0": (-1, 0),
+}
+
+
+def test_fused_backward_plans_match_the_recorded_ones():
+    """The launch plans of ieagan_conv1x1_bwd / ieagan_conv3x3_bwd (pure host code: runs without a GPU) -- blocks per image and slab workspace
+    at the train step's shapes and at the edge shapes of the GPU tests -- against the values the separate plans of both launchers gave
+    before they were folded onto one; and the retired occupancy bits of ieagan_conv1x1_bwd_desc.flags are refused."""
+    import _hip
+    if not os.path.exists(_hip.LIB_PATH):
+        pytest.skip("library not built")
+    lib = ctypes.CDLL(_hip.LIB_PATH)
+    cases = _fused_backward_plan_cases()
+    assert {k for k, _, _ in cases} == set(FUSED_BACKWARD_PLANS)
+    for key, stem, d in cases:
+        slots, ws = getattr(lib, stem + "_slots"), getattr(lib, stem + "_workspace")
+        slots.restype, ws.restype = ctypes.c_int, ctypes.c_long
+        slots.argtypes = ws.argtypes = [ctypes.c_void_p]
+        assert (slots(ctypes.byref(d)), ws(ctypes.byref(d))) == FUSED_BACKWARD_PLANS[key], key
+    # orientation: 6 / 9 / 6 / 5 blocks at the edge shapes
+    assert [FUSED_BACKWARD_PLANS[k][0] for k in ("1x1 64->16 N3 12x32 rs0 a0 e0 f0", "1x1 32->16 N3 24x64 rs0 a0 e0 f0", "3x3 C16 N3 16x64 rs0 a0 npe0",
+                                                  "3x3 C32 N5 8x32 rs0 a0 npe0")] == [2, 3, 2, 1]
+    lib.ieagan_conv1x1_bwd.restype = ctypes.c_int
+    lib.ieagan_conv1x1_bwd.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.ieagan_last_error.restype = ctypes.c_char_p
+    for bit in (1, 2):
+        d = _fused_backward_plan_cases()[0][2]
+        d.flags = bit
+        assert lib.ieagan_conv1x1_bwd_slots(ctypes.byref(d)) == -1                       # IEAGAN_EINVAL
+        assert lib.ieagan_conv1x1_bwd(ctypes.byref(d), None) == -1 and b"unknown flag bits" in lib.ieagan_last_error()

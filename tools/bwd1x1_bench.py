@@ -1,4 +1,4 @@
-"""Stand-alone timing of ieagan_conv1x1_bwd at the production shapes (N = 40), 2 vs 3 blocks per CU (development aid)."""
+"""Stand-alone timing of ieagan_conv1x1_bwd at the production shapes (N = 40), 32-pixel wave tiles vs the default (development aid)."""
 import os, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(root, "iea-gan_amd"), root]
@@ -48,7 +48,7 @@ for name, Cin, Cout, Hc, Wc, rs, aff, relu, eff, link, om, gout in CASES:
     if link is not None:
         moved += 2.0 * (P if om == 1 else Ps) * lCa * (4 if lmode == 1 else 0.25 if lmode == 2 else 1)
     line = f"{name:10s} {Cin:3d}->{Cout:3d} {Hc}x{Wc} rs{rs} a{aff} e{eff} l{lmode if link else -1}: {moved / 1e6:7.0f} MB "
-    for flags in (H.B1_OCC2 | H.B1_TP32, H.B1_OCC2, 0):
+    for flags in (H.B1_TP32, 0):
         d = H.Conv1x1BwdDesc(N, Hc, Wc, Cin, Cout, kpad, kpad2, H.src_desc(x, Cin, Hs, Ws, rs, sc, sh, Cin if aff else 0, relu), g.data_ptr(), Cout,
                              H.ptr(y), H.ptr(dstat), N, H.ptr(geff), wb.data_ptr(), H.ptr(lg), lC, lCa, lmode, dx.data_ptr(), om, H.ptr(acc),
                              dw.data_ptr(), None, cs.data_ptr(), flags)
@@ -65,5 +65,5 @@ for name, Cin, Cout, Hc, Wc, rs, aff, relu, eff, link, om, gout in CASES:
         e1.record()
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) / 20 * 1e3
-        line += f"| {('tp32' if flags & H.B1_TP32 else 'occ2' if flags else 'dflt')} {us:7.1f} us {moved / us / 1e6:5.2f} TB/s "
+        line += f"| {('tp32' if flags & H.B1_TP32 else 'dflt')} {us:7.1f} us {moved / us / 1e6:5.2f} TB/s "
     print(line, flush=True)
