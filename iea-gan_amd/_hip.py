@@ -182,6 +182,16 @@ _SIGS = {
     "ieagan_selftest_tr_read": [vp, vp, vp],
 }
 EXPORTS = ["ieagan_last_error"] + list(_SIGS)
+# the entry points of include/ieagan_pxd_tracking.h (csrc/pxd_doublets.hip), in the same library
+PXD_DOUBLET_COUNTERS = ("events", "inner_hits", "outer_hits", "doublets", "candidates")
+PXD_PARTNER_BINS = 64
+_SIGS_TRACKING = {
+    "ieagan_pxd_space_points": [vp] * 11 + [i, i, i, i, l] + [vp] * 8,
+    "ieagan_pxd_doublets_scratch": [i, i, l],
+    "ieagan_pxd_doublets": [vp] * 9 + [i, i, l, i, i, l] + [vp] * 8,
+    "ieagan_pxd_doublet_stats": [vp] * 8 + [i, i, l] + [vp] * 3,
+}
+EXPORTS_TRACKING = list(_SIGS_TRACKING)
 
 _lib = None
 
@@ -200,7 +210,7 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} has ABI version {_lib.ieagan_abi_version()}, the Python binding expects {ABI_VERSION}: "
                                "rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
         _lib.ieagan_last_error.restype = C.c_char_p
-        for name, sig in _SIGS.items():
+        for name, sig in (*_SIGS.items(), *_SIGS_TRACKING.items()):
             fn = getattr(_lib, name)
             fn.argtypes = sig
             fn.restype = C.c_long if name.endswith(("_workspace", "_scratch")) else C.c_int

@@ -4,7 +4,8 @@
 frame of a sensor with a geometry given as data (csrc/pxd_hits.hip), the event and hit files of ``produce.py`` and the store that keeps such a file's events on the device and expands them into the network input
 (csrc/pxd_events.hip), the overlay of the events of two stores, pixel by pixel in the sparse format (csrc/pxd_overlay.hip), the match of
 the signal hits to the hits of the mixed events, hit by hit (csrc/pxd_match.hip), and the correlations between the region occupancies of one
-event -- exact Pearson and Spearman tables from integer moments and ranks (csrc/pxd_corr.hip).  ``utils`` re-exports every name defined here."""
+event -- exact Pearson and Spearman tables from integer moments and ranks (csrc/pxd_corr.hip) --, and the hits in a global frame with the
+inner / outer-layer hit doublets of an event (csrc/pxd_doublets.hip).  ``utils`` re-exports every name defined here."""
 from __future__ import annotations
 
 import numpy as np
@@ -896,7 +897,8 @@ def pxd_hits(images_or_product, geometry, head_tail=3, threshold=0.0, seed_cut=0
     * ``position = float32(float64(num) / float64(den))``: ``num`` and ``den`` are exact integers below 2^53 (``PXDGeometry``), so the same
       recipe on the host gives the same bits; bit-identical run to run.
 
-    Position errors and signal-to-noise cuts (both need a per-pixel noise map), global coordinates and a basf2 writer are out of scope.
+    Position errors and signal-to-noise cuts (both need a per-pixel noise map) and a basf2 writer are out of scope; global coordinates are
+    ``pxd_space_points``.
     Launches on the current stream, neither synchronises nor copies; with ``capacity`` given it can be captured into a HIP graph.  When the
     digit total exceeds the capacity the device result covers the first ``capacity`` digits; ``PXDHits.cpu()`` reruns instead of handing
     back a truncated event.  ``ValueError`` when the geometry's ``H``, ``W`` or ``S`` are not the batch's."""
@@ -1509,3 +1511,370 @@ def pxd_match_distance(real, fake):
     width = float(real["residual_bin"]) * float(real["unit_mm"])
     return dict(out, residual_u_w1=_w1(real["residual_u"], fake["residual_u"], width), residual_v_w1=_w1(real["residual_v"], fake["residual_v"], width),
                 purity_w1=_w1(real["purity"], fake["purity"], 1.0 / PXD_PURITY_BINS))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# space points and inner / outer-layer hit doublets: the hits in a global frame, paired across the two layers (csrc/pxd_doublets.hip)
+# ---------------------------------------------------------------------------------------------------------
+PXD_SUB = 16                    # sub-units per geometry unit: u * 16.0f is exact in fp32
+PXD_COORD_LIMIT = 2 ** 23       # every corner of every sensor lies below this many sub-units from the origin, along every axis
+
+
+class PXDPlacement:
+    """Where the sensors sit in space, as data, in sub-units of 1 / 16 geometry unit (31.25 nm at the default ``unit_mm = 5e-4``):
+    ``origin`` int ``[S, 3]`` (the sensor centre), ``u_axis`` / ``v_axis`` int ``[S, 3]`` (the global directions of local u, the rows, and
+    local v, the columns, as Q30 integers, ``|a| <= 2**30``), ``layer`` int ``[S]`` (0 inner, 1 outer, -1 ignored) and ``pairs`` uint8
+    ``[S, S]``: a doublet of inner sensor ``i`` and outer sensor ``o`` counts only when ``pairs[i, o] != 0`` (default: 1 wherever ``layer[i]
+    == 0 and layer[o] == 1``; entries outside that pattern are always zeroed).  The integer tables are the geometry: ``origin``, ``u_axis``,
+    ``v_axis``, ``layer`` are int32 NumPy arrays, ``tables(device)`` gives their device copies, uploaded once per device on first use.
+
+    ``ValueError`` for shapes that disagree, more than 255 sensors, a ``layer`` outside ``-1 .. 1``, ``|axis| > 2**30`` and -- with
+    ``geometry`` (a ``PXDGeometry``) given here, else in ``pxd_space_points`` -- any sensor corner whose global coordinate reaches ``2**23``
+    sub-units.  That bound is what keeps ``pxd_doublets`` exact: ``|x|, |y|, |z| < 2**23`` and ``r < 2**23.5``, so ``x_a x_b + y_a y_b``
+    and the cross product stay below ``2**47``, ``tan_q12 * dot`` below ``2**62`` and ``z_a r_b - z_b r_a`` below ``2**48``."""
+    TABLES = ("origin", "u_axis", "v_axis", "layer", "pairs")
+
+    def __init__(self, origin, u_axis, v_axis, layer, pairs=None, unit_mm=5e-4, geometry=None):
+        o, ua, va, la = (np.asarray(a) for a in (origin, u_axis, v_axis, layer))
+        if la.ndim != 1 or la.size == 0 or any(a.shape != (la.size, 3) for a in (o, ua, va)) or any(a.dtype.kind not in "iu" for a in (o, ua, va, la)):
+            raise ValueError(f"PXDPlacement: origin {o.shape} / u_axis {ua.shape} / v_axis {va.shape} / layer {la.shape} are not integer arrays "
+                             "[S, 3], [S, 3], [S, 3] and [S]")
+        S = la.size
+        if S > 255:
+            raise ValueError(f"PXDPlacement: {S} sensors are more than 255")
+        o, ua, va, la = (a.astype(np.int64) for a in (o, ua, va, la))
+        if la.min() < -1 or la.max() > 1:
+            raise ValueError(f"PXDPlacement: layer holds {int(la.min())} .. {int(la.max())}, outside -1 .. 1")
+        if max(np.abs(ua).max(), np.abs(va).max()) > 2 ** 30:
+            raise ValueError("PXDPlacement: an axis component is beyond 2**30 in Q30")
+        if np.abs(o).max() >= PXD_COORD_LIMIT:
+            raise ValueError(f"PXDPlacement: a sensor centre reaches 2**23 sub-units ({int(np.abs(o).max())})")
+        pattern = ((la[:, None] == 0) & (la[None, :] == 1)).astype(np.uint8)
+        if pairs is None:
+            pairs = pattern
+        else:
+            pairs = np.asarray(pairs)
+            if pairs.shape != (S, S):
+                raise ValueError(f"PXDPlacement: pairs {pairs.shape} is not [S, S] = [{S}, {S}]")
+            pairs = (pairs != 0).astype(np.uint8) * pattern
+        self.origin, self.u_axis, self.v_axis, self.layer = (a.astype(np.int32) for a in (o, ua, va, la))
+        self.pairs, self.unit_mm, self.S, self._device, self._checked = np.ascontiguousarray(pairs), float(unit_mm), S, {}, []
+        if geometry is not None:
+            self.check_corners(geometry)
+
+    def check_corners(self, geometry):
+        """``ValueError`` when a corner of a sensor of ``geometry`` reaches ``2**23`` sub-units along a global axis, when the geometry has
+        other sensors or another unit; remembered per geometry."""
+        if any(g is geometry for g in self._checked):
+            return
+        if not isinstance(geometry, PXDGeometry):
+            raise TypeError("PXDPlacement: geometry must be a PXDGeometry")
+        if geometry.S != self.S or geometry.unit_mm != self.unit_mm:
+            raise ValueError(f"PXDPlacement: {self.S} sensors in units of {self.unit_mm} mm, the geometry has {geometry.S} in units of {geometry.unit_mm} mm")
+        half_u = (geometry.u_length[geometry.kind].astype(np.int64) * PXD_SUB + 1) // 2        # sub-units, rounded up
+        half_v = (geometry.v_length[geometry.kind].astype(np.int64) * PXD_SUB + 1) // 2
+        ua, va, o = (a.astype(np.int64) for a in (self.u_axis, self.v_axis, self.origin))
+        for su in (-1, 1):
+            for sv in (-1, 1):
+                corner = o + ((ua * (su * half_u)[:, None] + va * (sv * half_v)[:, None] + 2 ** 29) >> 30)
+                if np.abs(corner).max() >= PXD_COORD_LIMIT:
+                    s = int(np.argmax(np.abs(corner).max(1)))
+                    raise ValueError(f"PXDPlacement: a corner of sensor {s} reaches 2**23 sub-units ({int(np.abs(corner[s]).max())}): "
+                                     f"{PXD_COORD_LIMIT * self.unit_mm / PXD_SUB:.1f} mm is the limit at this unit")
+        self._checked.append(geometry)
+
+    def tables(self, device):
+        """The five tables on ``device`` (dict by name; int32, ``pairs`` uint8); the upload happens once per device."""
+        device = torch.device(device)
+        if device not in self._device:
+            self._device[device] = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device) for k in self.TABLES}
+        return self._device[device]
+
+    def same_as(self, other):
+        return self is other or (isinstance(other, PXDPlacement) and self.unit_mm == other.unit_mm and
+                                 all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self.TABLES))
+
+    @classmethod
+    def from_float(cls, origin_mm, u_axis, v_axis, layer, pairs=None, unit_mm=5e-4, geometry=None):
+        """Float tables rounded once, on the host: ``round(x / unit_mm * 16)`` for the origin in mm, ``round(a * 2**30)`` for the axes."""
+        o = np.rint(np.asarray(origin_mm, np.float64) / unit_mm * PXD_SUB).astype(np.int64)
+        ua, va = (np.rint(np.asarray(a, np.float64) * 2.0 ** 30).astype(np.int64) for a in (u_axis, v_axis))
+        return cls(o, ua, va, np.asarray(layer), pairs, unit_mm, geometry)
+
+    @classmethod
+    def barrel(cls, geometry, radii, ladders, per_ladder=2, pairs=None):
+        """Two concentric barrels for the sensors of ``geometry``, inner layer first: layer ``L`` has ``ladders[L]`` ladders at radius
+        ``radii[L]`` mm, ladder ``j`` at azimuth ``2 pi j / ladders[L]`` with a radial normal, u tangential towards increasing phi and v
+        along +z; the ``per_ladder`` sensors of a ladder lie end to end along z about z = 0 (sensor ``k`` centred at ``(k - (per_ladder -
+        1) / 2) * v_length``).  Sensor ``s = per_ladder * j + k`` in the inner layer, the outer layer follows.  No tilt."""
+        n = [int(v) for v in ladders]
+        per = int(per_ladder)
+        if len(n) != 2 or len(radii) != 2 or min(n) < 1 or per < 1 or per * sum(n) != geometry.S:
+            raise ValueError(f"PXDPlacement.barrel: ladders {tuple(ladders)} x {per_ladder} sensors are not the {geometry.S} sensors of the geometry")
+        origin, ua, va, layer = [], [], [], []
+        for L in (0, 1):
+            for j in range(n[L]):
+                phi = 2.0 * np.pi * j / n[L]
+                for k in range(per):
+                    s = len(layer)
+                    length = float(geometry.v_length[geometry.kind[s]]) * geometry.unit_mm
+                    origin.append([radii[L] * np.cos(phi), radii[L] * np.sin(phi), (k - (per - 1) / 2.0) * length])
+                    ua.append([-np.sin(phi), np.cos(phi), 0.0])
+                    va.append([0.0, 0.0, 1.0])
+                    layer.append(L)
+        return cls.from_float(origin, ua, va, layer, pairs, geometry.unit_mm, geometry)
+
+    @classmethod
+    def belle2(cls, geometry, radii=(14.0, 22.0), ladders=(8, 12)):
+        """The nominal Belle II PXD barrel for ``PXDGeometry.belle2``: eight inner ladders at radius 14.0 mm and twelve outer ladders at
+        22.0 mm, ladder ``j`` at azimuth ``2 pi j / n``, normals radial, u tangential towards increasing phi, v along +z, the two sensors
+        of a ladder end to end with centres at ``z = -+ v_length / 2``, no windmill tilt; sensor order of the reference's
+        ``create_g1.py:95`` (``s = 2 j + k`` in layer 1, ``16 + 2 j + k`` in layer 2).  These are design values written down from memory:
+        the reference holds no geometry, and neither the radii, the azimuth of ladder 0, the missing tilt nor which sensor of a ladder
+        lies forward have been checked against basf2.  Pass the true ``radii`` / ``ladders``, or the tables of the conditions database to
+        ``PXDPlacement`` itself, where it matters."""
+        return cls.barrel(geometry, radii, ladders, 2)
+
+
+class PXDSpacePoints(_PXDProduct):
+    """Device-side result of ``pxd_space_points``: the ``PXDHits`` it came from (``hits``), the ``placement``, and per hit row (the first
+    ``total`` written) ``x`` / ``y`` / ``z`` / ``r`` int32 in sub-units, ``sensor`` int32 and ``role`` int8 (the layer of the hit's sensor),
+    all ``[capacity]``; ``offsets`` int32 ``[N + 1]``, the exclusive prefix of ``counts``.  ``counts`` / ``total`` are those of the hits."""
+    _again = lambda self, capacity: pxd_space_points(self.hits._again(capacity), self.placement)
+    PER_HIT = ("x", "y", "z", "r", "sensor", "role")
+
+    def __init__(self, hits, placement, offsets, **arrays):
+        self.hits, self.placement, self.geometry, self.offsets = hits, placement, hits.geometry, offsets
+        self.seed_cut, self.charge_cut, self.head_tail = hits.seed_cut, hits.charge_cut, hits.head_tail
+        vars(self).update(arrays)
+        self._set_header(hits.header, hits)
+
+    def _columns(self):
+        return dict(digit_header=self.hits.positions.clusters.digits.header, header=self.header, offsets=self.offsets,
+                    **{k: getattr(self, k) for k in self.PER_HIT})
+
+    def cpu(self):
+        """One read-back (``pxd_read_back``: one copy, one wait) -> dict of NumPy arrays trimmed to the true total, one entry per hit:
+        ``x``, ``y``, ``z``, ``r`` (int32, sub-units), ``x_mm``, ``y_mm``, ``z_mm``, ``r_mm`` (float64: ``x * unit_mm / 16``), ``sensor``,
+        ``role``, ``event``; plus ``counts [N]`` and ``offsets [N + 1]``.  Never truncated (``_host_columns``)."""
+        N = self.shape[0]
+        host = self._host_columns(self._columns)
+        total = int(host["header"][N])
+        out = {k: host[k][:total].copy() for k in self.PER_HIT}
+        image = np.searchsorted(host["offsets"], np.arange(total), side="right") - 1
+        out.update((k + "_mm", out[k].astype(np.float64) * self.placement.unit_mm / PXD_SUB) for k in ("x", "y", "z", "r"))
+        return dict(out, event=(image // self.n_sensors).astype(np.int32), counts=host["header"][:N].copy(), offsets=host["offsets"].copy())
+
+
+def pxd_space_points(hits, placement):
+    """The hits of a ``PXDHits`` in the global frame of a ``PXDPlacement``, in sub-units of 1 / 16 geometry unit (csrc/pxd_doublets.hip).
+    With ``lu = int(rintf(u * 16.0f))`` (one exact fp32 multiply, one round to nearest even) and ``lv`` likewise, for ``c = x, y, z``:
+    ``X_c = origin[s, c] + ((u_axis[s, c] * lu + v_axis[s, c] * lv + 2**29) >> 30)`` with an int64 arithmetic shift, and ``r =
+    isqrt(x**2 + y**2)`` exactly; ``s`` is the sensor of the hit's cluster.  ``rintf`` is the last float of the chain: the same recipe in
+    Python integers gives the same numbers, and two calls write the same bytes.
+
+    Launches on the current stream, neither synchronises nor copies, and can be captured into a HIP graph.  ``ValueError`` when the
+    placement does not fit the hits' geometry (sensors, unit, a corner at or beyond ``2**23`` sub-units)."""
+    H.require_gpu()
+    if not isinstance(hits, PXDHits) or not isinstance(placement, PXDPlacement):
+        raise TypeError("pxd_space_points: expects the PXDHits of pxd_hits and a PXDPlacement")
+    placement.check_corners(hits.geometry)
+    p, c = hits.positions, hits.positions.clusters
+    N, Hh, Ww = hits.shape
+    dev, C = hits.u.device, hits.capacity
+    out = {k: torch.empty(C, dtype=torch.int8 if k == "role" else torch.int32, device=dev) for k in PXDSpacePoints.PER_HIT}
+    offsets = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    t = placement.tables(dev)
+    with torch.cuda.device(dev):
+        H.call("ieagan_pxd_space_points", *_ptrs(C, p.cluster), hits.total.data_ptr(), *_ptrs(C, c.first), c.total.data_ptr(),
+               hits.counts.data_ptr(), *_ptrs(C, hits.u, hits.v), *(t[k].data_ptr() for k in PXDPlacement.TABLES[:4]), N, Hh, Ww, hits.n_sensors,
+               C, *_ptrs(C, *(out[k] for k in PXDSpacePoints.PER_HIT)), offsets.data_ptr(), H.stream())
+    return PXDSpacePoints(hits, placement, offsets, **out)
+
+
+def pxd_doublet_windows(dphi=0.3, z0_mm=10.0, unit_mm=5e-4):
+    """The two windows of ``pxd_doublets`` as the integers that are the rule: ``tan_q12 = round(tan(dphi) * 4096)`` in ``1 .. 32768`` and
+    ``z0_sub = round(z0_mm / unit_mm * 16)`` in ``0 .. 2**23 - 1``; ``ValueError`` outside."""
+    dphi, z0_mm = float(dphi), float(z0_mm)
+    tan_q12 = int(round(np.tan(dphi) * 4096)) if 0.0 < dphi < np.pi / 2 else 0
+    z0_sub = int(round(z0_mm / unit_mm * PXD_SUB)) if z0_mm >= 0 else -1
+    if not 1 <= tan_q12 <= 32768:
+        raise ValueError(f"pxd_doublets: dphi = {dphi} rad gives tan_q12 = {tan_q12}, outside 1 .. 32768")
+    if not 0 <= z0_sub < PXD_COORD_LIMIT:
+        raise ValueError(f"pxd_doublets: z0_mm = {z0_mm} gives z0_sub = {z0_sub}, outside 0 .. 2**23 - 1")
+    return tan_q12, z0_sub
+
+
+class PXDDoublets:
+    """Device-side result of ``pxd_doublets``: the ``PXDSpacePoints`` (``points``), the windows ``tan_q12`` / ``z0_sub``, ``partners`` int32
+    ``[points.capacity]`` (the doublets of an inner hit row, 0 for every other row of an event), ``event_doublets`` int32 ``[E]``,
+    ``pair_doublets`` int32 ``[S, S]`` (per inner and outer sensor), ``total`` int32 ``[1]`` and the list ``inner`` / ``outer`` int32 ``[doublet_capacity]``: the hit rows of the first ``min(total,
+    doublet_capacity)`` doublets in ascending ``(inner, outer)`` order.  ``partners``, ``event_doublets``, ``pair_doublets`` and ``total`` are always whole.
+    ``header`` / ``counts`` are those of the hits."""
+
+    def __init__(self, points, tan_q12, z0_sub, doublet_capacity, **arrays):
+        self.points, self.placement, self.tan_q12, self.z0_sub, self.doublet_capacity = points, points.placement, tan_q12, z0_sub, doublet_capacity
+        vars(self).update((k, getattr(points, k)) for k in ("shape", "n_sensors", "threshold", "seed_cut", "charge_cut", "header", "counts", "capacity"))
+        vars(self).update(arrays)
+
+    def _columns(self):
+        return dict(digit_header=self.points.hits.positions.clusters.digits.header, header=self.header, offsets=self.points.offsets,
+                    total=self.total, partners=self.partners, event_doublets=self.event_doublets, inner=self.inner, outer=self.outer)
+
+    def cpu(self):
+        """One read-back (``pxd_read_back``: one copy, one wait) -> dict of NumPy arrays: ``inner`` / ``outer`` ``[total]`` (hit rows),
+        ``event`` ``[total]``, ``partners`` ``[hits]``, ``event_doublets`` ``[E]``, ``total``, ``tan_q12``, ``z0_sub``.  Never truncated:
+        when the digit total exceeds the hits' capacity the chain is run again, when ``total`` exceeds ``doublet_capacity`` the doublets
+        are (a second read-back, on those paths only)."""
+        N = self.shape[0]
+        host = pxd_read_back(**self._columns())
+        grow = int(host["digit_header"][N]) > self.capacity
+        if grow:
+            self.points._grow(int(host["digit_header"][N]))
+        if grow or int(host["total"][0]) > self.doublet_capacity:
+            again = _doublets(self.points, self.tan_q12, self.z0_sub, None if grow else int(host["total"][0]))
+            vars(self).update(vars(again))
+            host = pxd_read_back(**self._columns())
+            if int(host["total"][0]) > self.doublet_capacity:           # after a grown chain: the default capacity may not do either
+                vars(self).update(vars(_doublets(self.points, self.tan_q12, self.z0_sub, int(host["total"][0]))))
+                host = pxd_read_back(**self._columns())
+        total, hits = int(host["total"][0]), int(host["header"][N])
+        inner = host["inner"][:total].copy()
+        image = np.searchsorted(host["offsets"], inner, side="right") - 1
+        return dict(inner=inner, outer=host["outer"][:total].copy(), event=(image // self.n_sensors).astype(np.int32),
+                    partners=host["partners"][:hits].copy(), event_doublets=host["event_doublets"].copy(), total=total,
+                    tan_q12=self.tan_q12, z0_sub=self.z0_sub)
+
+
+def _doublets(points, tan_q12, z0_sub, capacity=None):
+    """``ieagan_pxd_doublets`` of a ``PXDSpacePoints`` with the integer windows; ``capacity`` (doublets) defaults to the hits' capacity."""
+    (N, _, _), S, dev, C = points.shape, points.n_sensors, points.x.device, points.capacity
+    D = C if capacity is None else int(capacity)
+    if D < 0:
+        raise ValueError("pxd_doublets: capacity is negative")
+    new = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    out = dict(partners=new(C), event_doublets=new(N // S), pair_doublets=new(S * S).view(S, S), total=new(1), inner=new(D), outer=new(D))
+    scratch = new(H.lib().ieagan_pxd_doublets_scratch(N, S, C))
+    with torch.cuda.device(dev):
+        H.call("ieagan_pxd_doublets", *_ptrs(C, *(getattr(points, k) for k in PXDSpacePoints.PER_HIT)), points.offsets.data_ptr(),
+               points.total.data_ptr(), points.placement.tables(dev)["pairs"].data_ptr(), N, S, C, tan_q12, z0_sub, D, *_ptrs(C, out["partners"]),
+               out["event_doublets"].data_ptr(), out["pair_doublets"].data_ptr(), out["total"].data_ptr(), *_ptrs(D, out["inner"], out["outer"]),
+               scratch.data_ptr(), H.stream())
+    return PXDDoublets(points, tan_q12, z0_sub, D, **out)
+
+
+def pxd_doublets(hits_or_points, placement=None, dphi=0.3, z0_mm=10.0, capacity=None):
+    """Inner / outer-layer hit doublets of a batch (csrc/pxd_doublets.hip): the first question tracking asks the PXD.  Input: a ``PXDHits``
+    with a ``PXDPlacement`` (``pxd_space_points`` runs first) or an existing ``PXDSpacePoints``.  The host turns the windows into integers
+    once (``pxd_doublet_windows``): ``tan_q12 = round(tan(dphi) * 4096)``, ``z0_sub = round(z0_mm / unit_mm * 16)``; the integers are the
+    rule.  Hit ``a`` with ``role == 0`` and hit ``b`` with ``role == 1`` of the same event form a doublet iff, in int64,
+
+    * ``pairs[sensor_a, sensor_b] != 0``;
+    * ``dot = x_a x_b + y_a y_b > 0`` and ``abs(x_a y_b - y_a x_b) << 12 <= tan_q12 * dot``: the azimuth window ``|dphi|``;
+    * ``r_b > r_a`` and ``abs(z_a r_b - z_b r_a) <= z0_sub * (r_b - r_a)``: the straight line through both hits in (r, z) meets the beam
+      line within ``+- z0``.
+
+    The list ``inner`` / ``outer`` holds the hit rows of every doublet in ascending ``(inner, outer)`` order, ``capacity`` of them
+    (default: the hits' capacity); on overflow it holds the first ``capacity`` of that order, ``partners`` / ``event_doublets`` /
+    ``pair_doublets`` / ``total`` stay whole and ``PXDDoublets.cpu()`` reruns with a larger capacity instead of returning a truncated list.  No float exists on the
+    device after ``rintf``: two calls write the same bytes.  Launches on the current stream, neither synchronises nor copies; with
+    ``capacity`` given it can be captured into a HIP graph.  Triplets with the SVD, curvature or pT windows, alignment, the windmill
+    geometry, doublets labelled by ``pxd_match`` truth and position errors are out of scope."""
+    H.require_gpu()
+    points = hits_or_points
+    if isinstance(points, PXDSpacePoints):
+        if placement is not None and not points.placement.same_as(placement):
+            raise ValueError("pxd_doublets: the PXDSpacePoints were made with another placement")
+    elif isinstance(points, PXDHits):
+        if placement is None:
+            raise TypeError("pxd_doublets: PXDHits need a placement")
+        points = pxd_space_points(points, placement)
+    else:
+        raise TypeError("pxd_doublets: expects the PXDHits of pxd_hits or the PXDSpacePoints of pxd_space_points")
+    return _doublets(points, *pxd_doublet_windows(dphi, z0_mm, points.placement.unit_mm), capacity)
+
+
+class PXDDoubletStatistics(_PXDAccumulator):
+    """Accumulator of the doublet statistics over batches, beside the other ``PXD*`` accumulators: how many hit pairs across the two layers
+    are compatible with one track from the interaction region -- the number that decides how many fake track seeds a background makes, and
+    that sees whether the hits of an event are spatially coherent.  ``update`` takes images, any chain product up to ``PXDHits``, a
+    ``PXDSpacePoints`` or a ``PXDDoublets``, runs what is missing and ``ieagan_pxd_doublet_stats`` on the current stream; it neither
+    synchronises nor copies, ``result()`` does the single read-back.  Counters are exact int64.  An update whose digit total exceeds the
+    ``capacity`` (digits) is counted on the device and makes ``result()`` raise.  The statistics never read the list of doublets, so the
+    ``doublet_capacity`` of the doublets an update makes (default: the digit capacity) bounds only that list.  ``tables``: int64 ``[5 +
+    S * S + 64 + 251 + 1]`` on the device, the overflow counter last."""
+    _per_image = ("hits",)
+
+    def __init__(self, placement, geometry, n_sensors=40, threshold=7.0, dphi=0.3, z0_mm=10.0, seed_cut=0, charge_cut=0, head_tail=3,
+                 capacity=None, doublet_capacity=None, device=None):
+        if not isinstance(placement, PXDPlacement) or not isinstance(geometry, PXDGeometry):
+            raise TypeError("PXDDoubletStatistics: expects a PXDPlacement and a PXDGeometry")
+        if placement.S != int(n_sensors):
+            raise ValueError(f"PXDDoubletStatistics: the placement has {placement.S} sensors, not {n_sensors}")
+        placement.check_corners(geometry)
+        self.placement, self.geometry, self.head_tail = placement, geometry, int(head_tail)
+        self.seed_cut, self.charge_cut = _check_cuts("PXDDoubletStatistics", seed_cut, charge_cut)
+        self.tan_q12, self.z0_sub = pxd_doublet_windows(dphi, z0_mm, placement.unit_mm)
+        self.doublet_capacity = doublet_capacity if doublet_capacity is None else int(doublet_capacity)
+        super().__init__(n_sensors, threshold, capacity, device)
+
+    def update(self, images_or_product):
+        d = self._input(images_or_product, "pxd_digits", PXDClusters, PXDClusterPositions, PXDHits, PXDSpacePoints, PXDDoublets)
+        if not isinstance(d, (PXDHits, PXDSpacePoints, PXDDoublets)):
+            d = pxd_hits(d, self.geometry, self.head_tail, self.threshold, self.seed_cut, self.charge_cut, self.capacity, self.n_sensors)
+        if isinstance(d, PXDHits):
+            d = pxd_space_points(d, self.placement)
+        if not self.placement.same_as(d.placement):
+            raise ValueError(f"PXDDoubletStatistics.update: the {type(d).__name__} was made with another placement")
+        if isinstance(d, PXDSpacePoints):
+            d = _doublets(d, self.tan_q12, self.z0_sub, self.doublet_capacity)
+        if (d.tan_q12, d.z0_sub) != (self.tan_q12, self.z0_sub):
+            raise ValueError(f"PXDDoubletStatistics.update: the PXDDoublets were made with the windows {(d.tan_q12, d.z0_sub)}, not {(self.tan_q12, self.z0_sub)}")
+        p, S, (N, _, _), C = d.points, self.n_sensors, d.shape, d.capacity
+        words = len(H.PXD_DOUBLET_COUNTERS) + S * S + H.PXD_PARTNER_BINS + H.PXD_BINS
+        if self.tables is None:
+            self.tables = torch.zeros(words + 1, dtype=torch.int64, device=self.device)
+        t = self.tables.data_ptr()
+        with torch.cuda.device(self.device):
+            H.call("ieagan_pxd_doublet_stats", *_ptrs(C, p.role), p.offsets.data_ptr(), p.total.data_ptr(),
+                   p.hits.positions.clusters.digits.total.data_ptr(), self.placement.tables(self.device)["layer"].data_ptr(), *_ptrs(C, d.partners),
+                   d.event_doublets.data_ptr(), d.pair_doublets.data_ptr(), N, S, C, t, t + 8 * words, H.stream())
+        self.hits.append(d.counts)
+        return d
+
+    def result(self):
+        """NumPy tables: int64 ``events``, ``inner_hits``, ``outer_hits``, ``doublets``, ``candidates`` (the sum over the events of ``n_in *
+        n_out``), ``sensor_pairs [S, S]`` (doublets per inner and outer sensor), ``partners_spectrum [64]`` (over the inner hits, last bin
+        open), ``event_doublets_spectrum [251]`` (over the events, the bins of ``pxd_bin_index``); float64 ``doublets_per_event`` and
+        ``acceptance = doublets / candidates`` (NaN without events / candidates); the windows ``tan_q12`` / ``z0_sub``, the placement's
+        ``origin`` / ``u_axis`` / ``v_axis`` / ``layer`` / ``pairs``, ``shape``; ``hits`` int32 ``[events, S]`` and ``n_events``.  Raises
+        when an update overflowed."""
+        table, per_image = self._host_tables()
+        S, n = self.n_sensors, len(H.PXD_DOUBLET_COUNTERS)
+        out = {k: int(table[i]) for i, k in enumerate(H.PXD_DOUBLET_COUNTERS)}
+        ratio = lambda a, b: float(a) / float(b) if b > 0 else float("nan")
+        return dict(out, sensor_pairs=table[n:n + S * S].reshape(S, S).copy(), partners_spectrum=table[n + S * S:n + S * S + H.PXD_PARTNER_BINS].copy(),
+                    event_doublets_spectrum=table[n + S * S + H.PXD_PARTNER_BINS:].copy(), doublets_per_event=ratio(out["doublets"], out["events"]),
+                    acceptance=ratio(out["doublets"], out["candidates"]), tan_q12=self.tan_q12, z0_sub=self.z0_sub, shape=self.shape,
+                    **{k: getattr(self.placement, k).copy() for k in PXDPlacement.TABLES}, hits=per_image["hits"], n_events=per_image["n_events"])
+
+
+def pxd_doublet_distance(real, fake):
+    """Four distances between two ``PXDDoubletStatistics.result()`` tables (float64, host): ``doublet_rate_rel_err`` = |fake - real| / real
+    of the doublets per event; ``acceptance_rel_err`` = the same of ``doublets / candidates``, the fraction of the inner x outer hit pairs
+    of an event that pass the windows -- the number that sees spatial coherence, whatever the occupancies are; ``partners_w1`` = the 1-D
+    Wasserstein distance between the normalised spectra of partners per inner hit; ``sensor_pair_l1`` = the L1 distance of the two
+    normalised ``[S, S]`` tables.  NaN where a real denominator is 0 or a side is empty.  ``ValueError`` when the windows, the placement
+    tables or the shapes differ."""
+    for k in ("tan_q12", "z0_sub", "shape"):
+        if tuple(np.atleast_1d(real[k])) != tuple(np.atleast_1d(fake[k])):
+            raise ValueError(f"pxd_doublet_distance: the two sides differ in {k}: {real[k]} and {fake[k]}")
+    for k in PXDPlacement.TABLES:
+        if not np.array_equal(real[k], fake[k]):
+            raise ValueError(f"pxd_doublet_distance: the two sides differ in the placement table {k}")
+    rel = lambda r, f: abs(f - r) / r if r == r and r > 0 and f == f else float("nan")
+    pr, pf = np.asarray(real["sensor_pairs"], np.float64), np.asarray(fake["sensor_pairs"], np.float64)
+    l1 = float(np.abs(pf / pf.sum() - pr / pr.sum()).sum()) if pr.sum() > 0 and pf.sum() > 0 else float("nan")
+    return dict(doublet_rate_rel_err=rel(real["doublets_per_event"], fake["doublets_per_event"]),
+                acceptance_rel_err=rel(real["acceptance"], fake["acceptance"]),
+                partners_w1=_w1(np.asarray(real["partners_spectrum"])[None], np.asarray(fake["partners_spectrum"])[None]), sensor_pair_l1=l1)

@@ -100,12 +100,13 @@ def test(G, D, G_ema, state_dict, config, test_log):
     test_log.log(itr=int(state_dict["itr"]), FID=float(FID))
 
 
-def generated_statistics(net, config, n_events, clusters=False, maps=False, correlations=False):
+def generated_statistics(net, config, n_events, clusters=False, maps=False, correlations=False, also=()):
     """A ``utils.PXDValidation`` over ``n_events`` events generated by ``net`` (eval mode when ``G_eval_mode``, no_grad, export epilogue):
     its ``.stats``, with ``clusters=True`` its ``.clusters`` and with ``maps=True`` or ``maps=(seed_cut, charge_cut)`` (ADU) its ``.maps``
     and with ``correlations=True`` or ``correlations=(RU, RV)`` its ``.correlations`` are fed.  The latents and ``rdof`` come from a
     ``torch.Generator`` of its own seeded with ``config['seed']``: the global generators
-    are not touched; the ``.training`` flags are restored.  No host synchronisation."""
+    are not touched; the ``.training`` flags are restored.  ``also``: further accumulators whose ``update`` gets every generated event.
+    No host synchronisation."""
     dev = next(net.parameters()).device
     n = int(config["n_classes"])
     gen = torch.Generator(device=dev).manual_seed(int(config["seed"]))
@@ -119,7 +120,10 @@ def generated_statistics(net, config, n_events, clusters=False, maps=False, corr
             for _ in range(n_events):
                 z = torch.randn(n, net.dim_z, generator=gen, device=dev)
                 rdof = torch.randn(n, net.rdof_dim, generator=gen, device=dev)
-                acc.update(net(z, y, rdof=rdof, export=True))
+                images = net(z, y, rdof=rdof, export=True)
+                acc.update(images)
+                for extra in also:
+                    extra.update(images)
     finally:
         net.train(was_training)
     return acc

@@ -1,9 +1,11 @@
-// Stand-alone check of the argument refusals of the thirteen launchers over the sparse digit list and the cluster table (csrc/pxd_clusters.hip,
-// pxd_reco.hip, pxd_hits.hip, pxd_overlay.hip, pxd_match.hip, pxd_corr.hip), for a sanitizer build of the host code:
+// Stand-alone check of the argument refusals of the sixteen launchers over the sparse digit list, the cluster table and the space points
+// (csrc/pxd_clusters.hip, pxd_reco.hip, pxd_hits.hip, pxd_overlay.hip, pxd_match.hip, pxd_corr.hip, pxd_doublets.hip), for a sanitizer build of
+// the host code:
 //
 //     hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Iinclude -Iiea-gan_amd/csrc \
 //           iea-gan_amd/csrc/pxd_clusters.hip iea-gan_amd/csrc/pxd_reco.hip iea-gan_amd/csrc/pxd_hits.hip iea-gan_amd/csrc/pxd_overlay.hip \
-//           iea-gan_amd/csrc/pxd_match.hip iea-gan_amd/csrc/pxd_corr.hip tools/pxd_argcheck.cpp -o pxd_argcheck && ./pxd_argcheck
+//           iea-gan_amd/csrc/pxd_match.hip iea-gan_amd/csrc/pxd_corr.hip iea-gan_amd/csrc/pxd_doublets.hip tools/pxd_argcheck.cpp \
+//           -o pxd_argcheck && ./pxd_argcheck
 //
 // Every call passes arguments a launcher must refuse before its first launch, so the program needs no GPU: it checks the return code and
 // the error text, prints every refusal as it was received, and exits 0 when every refusal came.  Per launcher it walks what the Python host
@@ -15,6 +17,7 @@
 
 #include "common.h"
 #include "ieagan_hip.h"
+#include "ieagan_pxd_tracking.h"
 
 static char g_err[512] = "";
 
@@ -52,6 +55,8 @@ struct S {
     int N = 4, H = 8, W = 8, n_sensors = 2, K = 1, head_tail = 3, seed_cut = 0, charge_cut = 0, residual_bin = 10, E = 1;
     long capacity = 16, m_capacity = 16, a_digits = 8, b_digits = 8;
     int a_events = 2, b_events = 2;
+    int tan_q12 = 1267, z0_sub = 320000;
+    long doublet_capacity = 16;
 };
 // One pointer argument: the text of its refusal when it is NULL and when it is `off` bytes off (nullptr: no such refusal, a byte array).
 struct Ptr {
@@ -294,6 +299,61 @@ static void corr() {
     expect(ieagan_pxd_ranks(x, 7, 18, x, nullptr), "rank2 must not be x", "rank2 == x");
 }
 
+// The three launchers of pxd_doublets.hip (include/ieagan_pxd_tracking.h) and the scratch size.
+static void tracking() {
+    const char *tt = "accepted_total / cluster_total is NULL or misaligned", *pl = "a placement table is NULL or not 4-byte aligned",
+               *co = "counts / offsets is NULL or not 4-byte aligned", *in = "cluster / first / u / v is NULL with capacity 16",
+               *out = "an output array is NULL with capacity 16", *al = "an int32 / fp32 array is not 4-byte aligned";
+#define SHAPE                                                                                                                         \
+    {[](S& s) { s.N = 0; }, "N = 0 outside 1 .. 65535", "N = 0"}, {[](S& s) { s.N = 65536; }, "outside 1 .. 65535", "N = 65536"},      \
+    {[](S& s) { s.n_sensors = 0; }, "n_sensors = 0 outside 1 .. 255", "n_sensors = 0"},                                               \
+    {[](S& s) { s.N = 512, s.n_sensors = 256; }, "n_sensors = 256 outside 1 .. 255", "n_sensors = 256"},                              \
+    {[](S& s) { s.n_sensors = 3; }, "N = 4 is not a multiple of n_sensors = 3", "n_sensors = 3"}, CAPACITY
+    const Ptr ptrs[] = {{"cluster", in, 2, al}, {"accepted_total", tt, 2, tt}, {"first", in, 2, al}, {"cluster_total", tt, 2, tt}, {"counts", co, 2, co},
+                        {"u", in, 2, al},       {"v", in, 1, al},              {"origin", pl, 2, pl}, {"u_axis", pl, 2, pl},       {"v_axis", pl, 1, pl},
+                        {"layer", pl, 2, pl},   {"x", out, 2, al},             {"y", out, 2, al},     {"z", out, 2, al},           {"r", out, 3, al},
+                        {"sensor", out, 2, al}, {"role", out, 0, nullptr},     {"offsets", co, 2, co}};
+    const Scalar scalars[] = {SHAPE, {[](S& s) { s.H = 0; }, "bad image size", "H = 0"}, {[](S& s) { s.W = -1; }, "bad image size", "W = -1"},
+                              {[](S& s) { s.N = 64, s.n_sensors = 64, s.H = s.W = 8192; }, "does not fit the int32 flat index", "2^32 pixels"}};
+    walk("pxd_space_points", ptrs, scalars, [](const P* p, const S& s) {
+        return ieagan_pxd_space_points(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], s.N, s.H, s.W, s.n_sensors, s.capacity, p[11],
+                                       p[12], p[13], p[14], p[15], p[16], p[17], nullptr);
+    });
+    const char *sp = "a space-point array is NULL with capacity 16", *a4 = "an int32 array is not 4-byte aligned",
+               *oe = "offsets / event_doublets / pair_doublets / total is NULL or not 4-byte aligned", *io = "inner / outer is NULL with doublet_capacity 16",
+               *sc = "scratch (", *at = "accepted_total is NULL or misaligned";
+    const Ptr dptrs[] = {{"x", sp, 2, a4},      {"y", sp, 2, a4},       {"z", sp, 2, a4},           {"r", sp, 2, a4},  {"sensor", sp, 1, a4},
+                         {"role", sp, 0, nullptr}, {"offsets", oe, 2, oe}, {"accepted_total", at, 2, at}, {"pairs", "pairs is NULL", 0, nullptr},
+                         {"partners", "partners is NULL with capacity 16", 2, a4}, {"event_doublets", oe, 2, oe}, {"pair_doublets", oe, 2, oe}, {"total", oe, 3, oe},
+                         {"inner", io, 2, a4},  {"outer", io, 2, a4},   {"scratch", sc, 2, sc}};
+    const Scalar dscalars[] = {SHAPE,
+                               {[](S& s) { s.doublet_capacity = -1; }, "doublet_capacity = -1 is negative", "doublet_capacity < 0"},
+                               {[](S& s) { s.tan_q12 = 0; }, "tan_q12 = 0 outside 1 .. 32768", "tan_q12 = 0"},
+                               {[](S& s) { s.tan_q12 = 32769; }, "tan_q12 = 32769 outside", "tan_q12 = 32769"},
+                               {[](S& s) { s.tan_q12 = -2147483647 - 1; }, "outside 1 .. 32768", "tan_q12 = INT_MIN"},
+                               {[](S& s) { s.z0_sub = -1; }, "z0_sub = -1 outside", "z0_sub = -1"},
+                               {[](S& s) { s.z0_sub = 1 << 23; }, "z0_sub = 8388608 outside 0 .. 2^23 - 1", "z0_sub = 2^23"}};
+    walk("pxd_doublets", dptrs, dscalars, [](const P* p, const S& s) {
+        return ieagan_pxd_doublets(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], s.N, s.n_sensors, s.capacity, s.tan_q12, s.z0_sub,
+                                   s.doublet_capacity, p[9], p[10], p[11], p[12], p[13], p[14], p[15], nullptr);
+    });
+    const char *t2 = "accepted_total / digit_total is NULL or misaligned", *ol = "offsets / layer / event_doublets / pair_doublets is NULL or not 4-byte aligned",
+               *to = "tables / overflow is NULL or not 8-byte aligned", *rp = "role / partners is NULL with capacity 16";
+    const Ptr sptrs[] = {{"role", rp, 0, nullptr}, {"offsets", ol, 2, ol},        {"accepted_total", t2, 2, t2}, {"digit_total", t2, 2, t2}, {"layer", ol, 2, ol},
+                         {"partners", rp, 2, "partners is not 4-byte aligned"}, {"event_doublets", ol, 1, ol}, {"pair_doublets", ol, 2, ol},
+                         {"tables", to, 4, to},    {"overflow", to, 4, to}};
+    const Scalar sscalars[] = {SHAPE};
+    walk("pxd_doublet_stats", sptrs, sscalars, [](const P* p, const S& s) {
+        return ieagan_pxd_doublet_stats(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], s.N, s.n_sensors, s.capacity, p[8], p[9], nullptr);
+    });
+#undef SHAPE
+    if (ieagan_pxd_doublets_scratch(40, 40, 480000) != 4 * (480000 / 256 + 1 + 1) || ieagan_pxd_doublets_scratch(0, 4, 16) != 0 ||
+        ieagan_pxd_doublets_scratch(4, 0, 16) != 0 || ieagan_pxd_doublets_scratch(4, 2, -1) != 0) {
+        std::printf("FAIL pxd_doublets_scratch\n");
+        ++failures;
+    }
+}
+
 int main() {
     clusters();
     reco();
@@ -301,6 +361,7 @@ int main() {
     overlay();
     match();
     corr();
+    tracking();
     std::printf("%s: %d refusal(s) received, %d missing\n", failures ? "FAILED" : "ok", refusals, failures);
     return failures ? 1 : 0;
 }
