@@ -18,6 +18,7 @@ CONV_FP8 = 4             # ieagan_conv_desc.flags bit: e4m3 MFMA operands in the
 CONV_FORCE_WS64 = 32     # ieagan_conv_desc.flags bit (tests / benchmarks): conv3x3_ws64 below its tile-count threshold too
 CONV_NO_WS64 = 16        # ieagan_conv_desc.flags bit (tests / benchmarks): C = 64 3x3 layers through conv3x3_lds instead of conv3x3_ws64
 CONV_NO_LDS_WEIGHTS = 2  # ieagan_conv_desc.flags bit: C = 64 / 128 3x3 layers through conv3x3_halo instead of conv3x3_lds
+CONV_FORCE_TILE = 64     # ieagan_conv_desc.flags bit (benchmarks): conv1x1_tile below its map-size floors too
 CONV_FORCE_GATHER = 1   # ieagan_conv_desc.flags bit (tests): route a 3x3 layer through the gather kernel
 B1_TP32 = 4  # ieagan_conv1x1_bwd_desc.flags bit (benchmarks): 32-pixel wave tiles everywhere
 BWD_NO_REDUCE = 16      # ieagan_conv1x1_bwd / ieagan_conv3x3_bwd: the caller folds the dW slabs (ieagan_wgrad_reduce)

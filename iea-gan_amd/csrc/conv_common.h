@@ -153,12 +153,14 @@ __device__ __forceinline__ void conv_epilogue_put(const f32x4 (&acc)[MTS][NT], f
 template <bool BNBOK, int NT, int MTS = 2, bool EARLY = true, typename PixFn>
 __device__ __forceinline__ void conv_epilogue_finish(const ConvArgs& a, const float* wlds, int n_base, PixFn pix,
                                                      float (&s1)[8], float (&s2)[8], const float* bias_pre = nullptr,
-                                                     const bf16x8* mask_pre = nullptr, const float* bnb_pre = nullptr) {
+                                                     const bf16x8* mask_pre = nullptr, const float* bnb_pre = nullptr,
+                                                     const bf16x8* res_pre = nullptr) {
     // bias_pre: this lane's 8 bias values (channel chunk lane % CPP), loaded once by a kernel that walks several tiles;
     // mask_pre: the ReLU-mask / BatchNorm-input chunks of this call's (16*MTS*CPP)/64 iterations, requested by the caller ahead of
     // time (same lane -> (row, chunk) mapping as below) so that their latency is not paid inside the epilogue;
     // bnb_pre: LDS copy of the BatchNorm-backward scale / shift rows of the image all pixels of this call belong to
-    // ([0, NT*16) scale, [NT*16, 2*NT*16) shift of channels n_base ..), instead of four global loads per chunk.
+    // ([0, NT*16) scale, [NT*16, 2*NT*16) shift of channels n_base ..), instead of four global loads per chunk;
+    // res_pre: like mask_pre, the same- or half-resolution residual chunks (A or B, whichever this lane's channels take) -- EARLY or not.
     constexpr int LDW = EpiLds<NT>::LDW;
     constexpr int CPP = NT * 2;                         // 8-channel chunks per pixel
     static_assert((16 * MTS * CPP) % 64 == 0, "epilogue rows x chunks must fill whole waves");
@@ -195,6 +197,10 @@ __device__ __forceinline__ void conv_epilogue_finish(const ConvArgs& a, const fl
         if (!ok_r[it]) continue;
         const long m = m_r[it];
         if (want_mask) mk_r[it] = *(const bf16x8*)((const bf16*)a.mask + m * a.Cout + co0);
+        if (res_pre != nullptr) {
+            rs_r[it] = res_pre[it];
+            continue;
+        }
         if (!EARLY) continue;
         if (ra_here && a.ra_rs == 0) rs_r[it] = *(const bf16x8*)((const bf16*)a.ra + m * a.Cra + co0);
         else if (ra_here && a.ra_rs == 1)      // operand lives at half resolution: nearest x2 upsample
@@ -247,7 +253,7 @@ __device__ __forceinline__ void conv_epilogue_finish(const ConvArgs& a, const fl
             float rv[8];
             if (a.ra_rs != 2) {
                 bf16x8 t = rs_r[it];
-                if (!EARLY) {
+                if (!EARLY && res_pre == nullptr) {
                     int n, h, w;
                     long mm;
                     pix(row, mm, n, h, w);
@@ -270,7 +276,7 @@ __device__ __forceinline__ void conv_epilogue_finish(const ConvArgs& a, const fl
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] += a.ra_scale * rv[i];
         } else if (rb_here) {
-            const bf16x8 t = EARLY ? rs_r[it] : *(const bf16x8*)((const bf16*)a.rb + m * a.Crb + (co0 - a.Ca));
+            const bf16x8 t = (EARLY || res_pre != nullptr) ? rs_r[it] : *(const bf16x8*)((const bf16*)a.rb + m * a.Crb + (co0 - a.Ca));
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] += bf2f(t[i]);
         }
@@ -292,9 +298,9 @@ __device__ __forceinline__ void conv_epilogue_finish(const ConvArgs& a, const fl
 template <bool BNBOK, int NT, int MTS = 2, bool EARLY = true, typename PixFn>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x4 (&acc)[MTS][NT], float* wlds, int n_base, PixFn pix,
                                               float (&s1)[8], float (&s2)[8], const float* bias_pre = nullptr,
-                                              const bf16x8* mask_pre = nullptr) {
+                                              const bf16x8* mask_pre = nullptr, const bf16x8* res_pre = nullptr) {
     conv_epilogue_put<NT, MTS>(acc, wlds);
-    conv_epilogue_finish<BNBOK, NT, MTS, EARLY>(a, wlds, n_base, pix, s1, s2, bias_pre, mask_pre);
+    conv_epilogue_finish<BNBOK, NT, MTS, EARLY>(a, wlds, n_base, pix, s1, s2, bias_pre, mask_pre, nullptr, res_pre);
 }
 
 

@@ -93,6 +93,7 @@ typedef struct {
 #define IEAGAN_CONV_NO_LDS_WEIGHTS 2   /* tests / benchmarks: C = 64 / 128 3x3 layers through conv3x3_halo instead of conv3x3_lds */
 #define IEAGAN_CONV_NO_WS64 16         /* tests / benchmarks: C = 64 3x3 layers through conv3x3_lds instead of the wave-specialised conv3x3_ws64 */
 #define IEAGAN_CONV_FORCE_WS64 32      /* tests / benchmarks: conv3x3_ws64 below its tile-count threshold too (its geometric preconditions still apply) */
+#define IEAGAN_CONV_FORCE_TILE 64      /* benchmarks: 1x1 layers through conv1x1_tile below its map-size floors too (its geometric preconditions still apply) */
 int ieagan_conv_forward(const ieagan_conv_desc* d, void* stream);
 /* blocks per statistics group of the launch ieagan_conv_forward(d) would make (the kernel selection and its grid are decided exactly as in
  * the real call, nothing is launched); < 0 on error.  Size `stats` with it and pass it as stats_slots. */
